@@ -12,9 +12,12 @@ block-cyclically column-split over the N ranks ("scaling": "strong", BASELINE co
 --config unblocked selects configs[1] (8192 x 8192, rank-1 path, HBM roofline).
 
 value = F(m,n) / t with F = 2 m n^2 - 2/3 n^3 (the reference's flop count).
-The JSON line also carries ||A-QR||_F/||A||_F of the last factorisation, `roofline` for the
-dominant kernel group (hipEvent-timed on the launch stream inside the timed region) and, at
-N = 1, `cpu_baseline` = the oracle's restatement of the reference algorithm on the host cores.
+A plain run sets up, warms up, times the K steps and prints the headline line (`ms_per_step` = one
+timed step).  With --full the JSON line also carries ||A-QR||_F/||A||_F of the last factorisation,
+`roofline` for the dominant kernel group (hipEvent-timed on the launch stream inside the timed
+region) and, at N = 1, `also` (the other configurations), micro-benchmarks and `cpu_baseline` =
+the oracle's restatement of the reference algorithm on the host cores.  --dump-outputs DIR writes
+the factors of the last timed step as .npy files (dump_outputs).
 
 N > 1 runs under a SUPERVISOR (this file, no GPU work of its own): every rank's bench.py starts the real run as a child
 process and watches its progress lines.  A child that makes no progress for DHQR_BENCH_STALL_S seconds (a collective that
@@ -368,7 +371,7 @@ def tallskinny(args, pkg, torch, dist, world, rank, local_rank, dev, spmd, attem
         barrier()
         progress(f"warm-up step {i + 1}/{args.warmup}")
     barrier()
-    if mg is not None:
+    if mg is not None and args.full:
         mg.reset_stats()
         mg.set_profiling(True)
     cc0 = mg.comm_counters(0) if mg is not None else q.comm.counters()
@@ -380,15 +383,18 @@ def tallskinny(args, pkg, torch, dist, world, rank, local_rank, dev, spmd, attem
     progress(f"{args.steps} timed steps done")
     cc1 = mg.comm_counters(0) if mg is not None else q.comm.counters()
     st = None
-    if mg is not None:
+    if mg is not None and args.full:
         st = mg.stats(0)
         mg.set_profiling(False)
+    if args.dump_outputs:  # (a one-process-per-GPU run was refused at the start)
+        dump_outputs(args.dump_outputs, *mg.rs_download())
+        progress(f"outputs written to {args.dump_outputs}")
     if spmd:
         t = torch.tensor([dt], dtype=torch.float64)  # host tensor: the control plane is gloo
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     resid = None
-    if not args.no_residual:
+    if args.full and not args.no_residual:
         resid = mg.rs_residual(0) if mg is not None else q.residual(0)
     value = flops_qr(m, n) / (dt / args.steps) / 1e9
     nranks = world if world > 1 else (args.logical_ranks or 1)
@@ -426,6 +432,35 @@ def tallskinny(args, pkg, torch, dist, world, rank, local_rank, dev, spmd, attem
 def emit(out, rank=0):
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: a factor of more elements is sampled (16 MiB of values + 16 MiB of their indices)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(d, A, alpha):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the factors (src:296-309: `A` = V on and
+    below the diagonal, R strictly above; `alpha` = diag(R)) -- as float64 .npy files in `d`.  A factor of more than
+    DUMP_SAMPLE elements is written as a fixed, seeded sample: A_sample.npy holds its elements at the column-major linear
+    indices (i + j*m) of A_sample_index.npy (float64, exact below 2^53).  `A` is a column-major device tensor (lda = m) or a
+    Fortran-ordered host array; `alpha` a device tensor or a host array."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    m, n = A.shape
+    host = isinstance(A, np.ndarray)
+    np.save(os.path.join(d, "alpha.npy"), np.asarray(alpha if isinstance(alpha, np.ndarray) else alpha.cpu().numpy(), dtype=np.float64))
+    if m * n <= DUMP_SAMPLE:
+        np.save(os.path.join(d, "A.npy"), np.asarray(A if host else A.cpu().numpy(), dtype=np.float64))
+        return
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, m * n, DUMP_SAMPLE, dtype=np.int64))
+    if host:
+        vals = np.ravel(A, order="F")[idx]
+    else:
+        import torch
+        assert A.stride() == (1, m), "dump_outputs: expected a column-major matrix with lda = m"
+        vals = A.t().reshape(-1)[torch.from_numpy(idx).to(A.device)].cpu().numpy()
+    np.save(os.path.join(d, "A_sample.npy"), vals.astype(np.float64))
+    np.save(os.path.join(d, "A_sample_index.npy"), idx.astype(np.float64))
 
 
 def pmc_traffic(symbol, m, n, nb, launches, work):
@@ -723,17 +758,28 @@ def main():
                          "tallskinny = configs[4] (262144x4096, rows split over the ranks, all-reduce of partial dots)")
     ap.add_argument("--n", type=int, default=0, help="matrix order (default 32768 blocked / 8192 unblocked)")
     ap.add_argument("--m", type=int, default=0, help="rows (default = n)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-residual", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure: the residual, hipEvent roofline per kernel "
+                         "group, power / clock telemetry, micro-benchmarks, the other configurations (`also`), the host-in / "
+                         "host-out call and the CPU baselines.  Without it a run sets up, warms up, times the steps and prints "
+                         "the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the factors of the last timed step to DIR/<name>.npy (float64; a large "
+                         "matrix as a fixed seeded sample, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-residual", action="store_true", help="with --full: skip ||A-QR||/||A||")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the other single-GPU configurations (unblocked 8192^2, row split 262144x4096 at world size 1) "
-                         "that the default 1-GPU run appends to its line as `also`")
+                    help="with --full: skip the other single-GPU configurations (unblocked 8192^2, row split 262144x4096 at "
+                         "world size 1) that a --full 1-GPU run appends to its line as `also`")
     ap.add_argument("--logical-ranks", type=int, default=0,
                     help="development: run R ranks of the multi-GPU driver on ONE GPU (in-process peer-copy transport)")
     ap.add_argument("--worker", action="store_true", help="internal: the measured run itself (started by the supervisor of N > 1)")
     args = ap.parse_args()
 
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and env_world > 1:
+        raise SystemExit("--dump-outputs: every rank of a one-process-per-GPU run holds only its own columns; "
+                         "run `python bench.py --gpus N` (one process drives the N GPUs) to dump the whole factorisation")
     if (args.gpus > 1 or env_world > 1) and not args.worker:
         if env_world > 1 and env_world != args.gpus:
             raise SystemExit(f"WORLD_SIZE={env_world} but --gpus {args.gpus}")
@@ -823,64 +869,37 @@ def main():
         barrier()
         progress(f"warm-up step {i + 1}/{args.warmup}")
     barrier()
-    if mode == "mg":
-        mg.reset_stats()
-        mg.set_profiling(True)
-        for r in range(mg.ndev):
-            mg.comm_timing(r, on=1)
-    else:
-        ctx.reset_stats()
-        ctx.set_profiling(True)
-        if mode == "spmd":
-            q.comm.timing(on=1)
-    try:
-        _pr = torch.cuda.get_device_properties(local_rank)
-        _pci = "%04x:%02x:%02x.0" % (_pr.pci_domain_id, _pr.pci_bus_id, _pr.pci_device_id)
-    except Exception:
-        _pci = None
-    tele = GpuTelemetry(local_rank, pci=_pci)
-    tele.start()
+    if args.full:  # hipEvent pairs around the launch groups (roofline, phases) and the telemetry thread: --full only
+        if mode == "mg":
+            mg.reset_stats()
+            mg.set_profiling(True)
+            for r in range(mg.ndev):
+                mg.comm_timing(r, on=1)
+        else:
+            ctx.reset_stats()
+            ctx.set_profiling(True)
+            if mode == "spmd":
+                q.comm.timing(on=1)
+        try:
+            _pr = torch.cuda.get_device_properties(local_rank)
+            _pci = "%04x:%02x:%02x.0" % (_pr.pci_domain_id, _pr.pci_bus_id, _pr.pci_device_id)
+        except Exception:
+            _pci = None
+        tele = GpuTelemetry(local_rank, pci=_pci)
+        tele.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    telemetry = tele.result()
+    telemetry = tele.result() if args.full else None
     progress(f"{args.steps} timed steps done")
-    per_rank = comm_t = None
-    if mode == "mg":
-        per_rank = [mg.stats(r) for r in range(mg.ndev)]
-        comm_t = [mg.comm_timing(r, on=0) for r in range(mg.ndev)]
-        mg.set_profiling(False)
-        st = per_rank[0]
-        panel_counts = [sum(s_["panels_fast"] for s_ in per_rank), sum(s_["panels_fallback"] for s_ in per_rank)]
-    else:
-        st = ctx.stats()
-        ctx.set_profiling(False)
-        panel_counts = list(ctx.panel_counters())
-        if mode == "spmd":
-            comm_t = q.comm.timing(on=0)
     if spmd:
         t = torch.tensor([dt], dtype=torch.float64)  # host tensor: the control plane is gloo
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-
-    resid = None
-    if not args.no_residual:
-        if mode == "single":
-            H = pkg.DistributedHouseholderQRStruct(A, alpha)
-            A0 = pkg.rand_colmajor(m, n, seed, dev)
-            resid = pkg.residual(H, A0)
-            del A0
-        elif mode == "mg":
-            resid = mg.residual(seed)
-        else:
-            resid = q.residual(seed)
-
     ms_step = dt / args.steps * 1e3
     value = flops_qr(m, n) / (dt / args.steps) / 1e9
-    dom, rl_all = roofline_groups(st, args.steps, m, n, nb)
-
     if mode == "single":
         par = "single GPU"
     elif mode == "mg":
@@ -897,6 +916,57 @@ def main():
                                (f"blocked nb=128 (BASELINE configs[{2 if world == 1 else 3}])" if nb else
                                 "unblocked rank-1 (BASELINE configs[1])"),
                    "m": m, "n": n, "nb": nb, "parallelism": par},
+        **attempt_fields(attempt),
+    }
+
+    def dump():  # single and one-process multi-GPU runs (a one-process-per-GPU run was refused at the start)
+        dump_outputs(args.dump_outputs, *((A, alpha) if mode == "single" else mg.download()))
+        progress(f"outputs written to {args.dump_outputs}")
+
+    def finish():
+        if mg is not None:
+            mg.close()
+        if spmd:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        if args.dump_outputs:
+            dump()
+        emit(out, rank)
+        return finish()
+
+    # --full: everything beside the headline figure
+    per_rank = comm_t = None
+    if mode == "mg":
+        per_rank = [mg.stats(r) for r in range(mg.ndev)]
+        comm_t = [mg.comm_timing(r, on=0) for r in range(mg.ndev)]
+        mg.set_profiling(False)
+        st = per_rank[0]
+        panel_counts = [sum(s_["panels_fast"] for s_ in per_rank), sum(s_["panels_fallback"] for s_ in per_rank)]
+    else:
+        st = ctx.stats()
+        ctx.set_profiling(False)
+        panel_counts = list(ctx.panel_counters())
+        if mode == "spmd":
+            comm_t = q.comm.timing(on=0)
+    if args.dump_outputs:
+        dump()
+
+    resid = None
+    if not args.no_residual:
+        if mode == "single":
+            H = pkg.DistributedHouseholderQRStruct(A, alpha)
+            A0 = pkg.rand_colmajor(m, n, seed, dev)
+            resid = pkg.residual(H, A0)
+            del A0
+        elif mode == "mg":
+            resid = mg.residual(seed)
+        else:
+            resid = q.residual(seed)
+
+    dom, rl_all = roofline_groups(st, args.steps, m, n, nb)
+    out.update({
         "residual": resid,
         "roofline": ({k: dom[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "launches",
                                           "launches_per_step", "avg_launch_ms", "ms_per_step", "traffic_bytes_per_step",
@@ -921,10 +991,9 @@ def main():
                         "the kernel sources still have the git blob ids stamped into profiles/pmc_traffic_current.json, "
                         "otherwise null with the reason",
         "gpu_telemetry": telemetry,
-        **attempt_fields(attempt),
         "phase_ms_per_step": {k: st[k] / args.steps for k in st if k.startswith("ms_") and st[k] > 0},
         "panels_fast_fallback": panel_counts,
-    }
+    })
     if mode == "mg" and mg.transport == "rccl":
         out["bcast_tuning"] = mg.bcast_tuning()
         out["rccl_nranks"] = mg.rccl_nranks()
@@ -1002,11 +1071,7 @@ def main():
             out["cpu_baseline"]["lapack_dgeqrf"] = cpu_baseline_lapack()
             out["host_cores"] = os.cpu_count()
     emit(out, rank)
-    if mg is not None:
-        mg.close()
-    if spmd:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -7,9 +7,9 @@ if [ "$1" != "skip-tests" ]; then
 ( timeout 1700 python -m pytest tests -m gpu -q --timeout 900 -rfEs -p no:cacheprovider 2>&1 | tail -15 ) > $O/pytest_gpu.txt; tail -3 $O/pytest_gpu.txt
 fi
 ( timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu | tail -4 ) > $O/smoke.txt; cat $O/smoke.txt
-timeout 1200 python bench.py > $O/bench_blocked32768.json 2> $O/bench_blocked32768.err; tail -c 400 $O/bench_blocked32768.json
+timeout 1200 python bench.py --full > $O/bench_blocked32768.json 2> $O/bench_blocked32768.err; tail -c 400 $O/bench_blocked32768.json
 ( for nb in 64 0; do timeout 300 python tools/c64_bench.py 8192 $nb 2>&1 | grep -v amdgpu | tail -1; done ) > $O/bench_complex8192.txt
-( for LR in 1 2 4 8; do timeout 300 python bench.py --logical-ranks $LR --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('logical ranks', $LR, 'ms', d['ms_per_step'], 'GFLOP/s', d['value'], 'resid', d.get('residual'), 'per-rank', d.get('per_rank_ms_per_step'))"; done ) > $O/logical_ranks.txt
+( for LR in 1 2 4 8; do timeout 300 python bench.py --full --logical-ranks $LR --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('logical ranks', $LR, 'ms', d['ms_per_step'], 'GFLOP/s', d['value'], 'resid', d.get('residual'), 'per-rank', d.get('per_rank_ms_per_step'))"; done ) > $O/logical_ranks.txt
 ( timeout 600 python tools/quick_bench.py 8192,128 16384,128 24576,128 12288,0 16384,0 2>/dev/null | grep '^{' | python -c "
 import sys,json
 for l in sys.stdin:

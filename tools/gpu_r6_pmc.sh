@@ -13,4 +13,4 @@ cd $R
 find $O/pmc -name "*kernel_trace.csv" -delete; find $O/pmc -name "*agent_info.csv" -delete
 python tools/pmc_summary.py $O/pmc $O/pmc_summary.json > $O/pmc_summary.txt 2>&1; python tools/pmc_stamp.py $O/pmc 32768 "round 6 final tree" > $O/pmc_stamp.txt 2>&1; cp profiles/pmc_traffic_current.json $O/pmc_traffic_current.json
 tail -4 $O/pmc_stamp.txt
-timeout 600 python bench.py --no-also > $O/bench_noalso.json 2> $O/bench.err; tail -c 700 $O/bench_noalso.json
+timeout 600 python bench.py --full --no-also > $O/bench_noalso.json 2> $O/bench.err; tail -c 700 $O/bench_noalso.json
