@@ -14,6 +14,8 @@ import os
 import numpy as np
 import pytest
 
+from layout_helpers import assert_guards_intact, each_layout, guarded_matrix, guarded_vector
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 P = ctypes.c_void_p
@@ -507,3 +509,142 @@ def test_argument_validation_and_empty_matrix(emu):
     assert emu.dhqr_solve_f64(h, _ptr(A), 8, 0, 8, None, None) == 0
     assert emu.dhqr_factor_f64(None, _ptr(A), 8, 4, 8, _ptr(al), 0) == -1         # null context
     emu.dhqr_destroy(h)
+
+
+# ---------------------------------------------------------------------------------------------------
+# The layouts a caller may pass (layout_helpers.LAYOUTS: lda > m even / odd / wide, a base 8 bytes off a 16-byte
+# boundary) inside buffers poisoned outside the window: the host dispatch (16-byte or scalar operand path, chosen from
+# lda % 2, rows % 2 and each pointer's alignment) and every stride, before a GPU visit.  tests/test_gpu_layouts.py runs the
+# same on the device.
+def _qtb(Ho, b):
+    y = np.array(b)
+    for j in range(Ho.shape[1]):
+        y[j:] -= Ho[j:, j] * (Ho[j:, j] @ y[j:])
+    return y
+
+
+def _check_layout(G, al, Ho, ao, tol=1e-12):
+    scale = np.abs(Ho).max()
+    eH, ea = np.abs(G.view - Ho).max(), np.abs(al.view - ao).max()
+    assert eH <= tol * scale and ea <= tol * scale, f"|dH| = {eH / scale:.2e}, |dalpha| = {ea / scale:.2e} (max|H|)"
+
+
+@pytest.mark.parametrize("m,n,nb", [(60, 20, 0), (201, 33, 0), (200, 130, 128), (300, 256, 128),
+                                    pytest.param(700, 512, 128, marks=_SLOW)])
+def test_factor_drivers_on_guarded_layouts(emu, orc, m, n, nb):
+    h = _ctx(emu)
+    A0 = orc.rand_matrix(m, n, 3)
+    Ho, ao = orc.householder(A0)
+
+    def run(lda, off):
+        G, al = guarded_matrix(m, n, lda, off, content=A0), guarded_vector(n, off)
+        assert emu.dhqr_factor_f64(h, P(G.ptr), m, n, lda, P(al.ptr), nb) == 0, emu.dhqr_last_error()
+        assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+        _check_layout(G, al, Ho, ao)
+        assert_guards_intact(G, "A")
+        assert_guards_intact(al, "alpha")
+
+    try:
+        each_layout(m, run)
+    finally:
+        emu.dhqr_destroy(h)
+
+
+@pytest.mark.parametrize("m,n,env", [(300, 200, {}), (777, 130, {}), (129, 129, {}), (260, 257, {"DHQR_TUNE": "qtb_vec=2"}),
+                                     pytest.param(1100, 1000, {"DHQR_TUNE": "qtb_vec=2"}, marks=_SLOW)])
+def test_pipelined_solve_on_guarded_layouts(emu, orc, m, n, env):
+    """dhqr_solve_f64 (dhqr_qtb.h) on the oracle's factor in every layout, b aligned and 8 bytes off: x, the Q'b left below
+    the triangle, the guards of b, and A / alpha untouched"""
+    A0 = orc.rand_matrix(m, n, 31)
+    Ho, ao = orc.householder(A0)
+    b = orc.rand_vector(m, 32)
+    xo = orc.solve(Ho, ao, b)
+    qtb = _qtb(Ho, b)
+    h = _ctx(emu, **env)
+
+    def run(lda, off):
+        G, al = guarded_matrix(m, n, lda, off, content=Ho), guarded_vector(n, off, content=ao)
+        bits = (G.bits().copy(), al.bits().copy())
+        for boff in (0, 1):
+            bg = guarded_vector(m, boff, content=b)
+            assert emu.dhqr_solve_f64(h, P(G.ptr), m, n, lda, P(al.ptr), P(bg.ptr)) == 0, emu.dhqr_last_error()
+            assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+            assert np.abs(bg.view[:n] - xo).max() <= 1e-10 * np.abs(xo).max(), f"b off {boff}: x"
+            if m > n:
+                assert np.abs(bg.view[n:] - qtb[n:]).max() <= 1e-12 * max(1.0, np.abs(qtb).max()), f"b off {boff}: Q'b tail"
+            assert_guards_intact(bg, f"b (off {boff})")
+        assert np.array_equal(G.bits(), bits[0]) and np.array_equal(al.bits(), bits[1]), "the solve wrote into A or alpha"
+
+    try:
+        each_layout(m, run)
+    finally:
+        emu.dhqr_destroy(h)
+
+
+@pytest.mark.parametrize("m,n", [(111, 100), (64, 64), (130, 20)] + [
+    pytest.param(m, n, marks=_SLOW) for m, n in ((220, 200), (256, 192))])
+def test_small_route_on_guarded_layouts(emu, orc, m, n):
+    """the single-workgroup route on device pointers: k_small_qr_d and k_small_ldiv run on the caller's lda and pointers"""
+    A0 = orc.rand_matrix(m, n, 41)
+    Ho, ao = orc.householder(A0)
+    b = orc.rand_vector(m, 42)
+    xo = orc.solve(Ho, ao, b)
+    qtb = _qtb(Ho, b)
+    h = _ctx(emu, DHQR_SMALL=1)
+
+    def run(lda, off):
+        G, al = guarded_matrix(m, n, lda, off, content=A0), guarded_vector(n, off)
+        assert emu.dhqr_factor_f64(h, P(G.ptr), m, n, lda, P(al.ptr), 0) == 0, emu.dhqr_last_error()
+        assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+        _check_layout(G, al, Ho, ao)
+        bits = (G.bits().copy(), al.bits().copy())
+        for boff in (0, 1):
+            bg = guarded_vector(m, boff, content=b)
+            assert emu.dhqr_solve_f64(h, P(G.ptr), m, n, lda, P(al.ptr), P(bg.ptr)) == 0, emu.dhqr_last_error()
+            assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+            assert np.abs(bg.view[:n] - xo).max() <= 1e-10 * np.abs(xo).max(), f"b off {boff}: x"
+            if m > n:
+                assert np.abs(bg.view[n:] - qtb[n:]).max() <= 1e-12 * max(1.0, np.abs(qtb).max()), f"b off {boff}: Q'b tail"
+            assert_guards_intact(bg, f"b (off {boff})")
+        assert np.array_equal(G.bits(), bits[0]) and np.array_equal(al.bits(), bits[1]), "the solve wrote into A or alpha"
+        assert_guards_intact(G, "A")
+        assert_guards_intact(al, "alpha")
+
+    try:
+        each_layout(m, run)
+        assert _counters(emu, h) == (0, 0)  # no panel went through the blocked drivers
+    finally:
+        emu.dhqr_destroy(h)
+
+
+def test_complex_entry_points_on_guarded_layouts(emu, orc):
+    """dhqr_factor_c64 / dhqr_solve_c64 with lda = m + 1 complex elements at a base one complex element in (16-byte
+    aligned: must work); a base 8 bytes off is DHQR_EINVAL and leaves the buffer bit for bit as it was"""
+    m, n = 150, 90
+    A0 = orc.rand_matrix_c(m, n, 8)
+    Ho, ao = orc.householder_c(A0)
+    b = orc.rand_vector_c(m, 9)
+    xo = orc.solve_c(Ho, ao, b)
+    h = _ctx(emu)
+
+    def run(lda, off):
+        G = guarded_matrix(m, n, lda, off, dtype=np.complex128, content=A0)
+        al = guarded_vector(n, off, dtype=np.complex128)
+        bits = G.bits().copy()
+        assert emu.dhqr_factor_c64(h, P(G.ptr + 8), m, n, lda, P(al.ptr)) == -1
+        assert b"16-byte" in emu.dhqr_last_error()
+        assert np.array_equal(G.bits(), bits), "a rejected call changed the matrix"
+        assert emu.dhqr_factor_c64(h, P(G.ptr), m, n, lda, P(al.ptr)) == 0, emu.dhqr_last_error()
+        assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+        _check_layout(G, al, Ho, ao)
+        bg = guarded_vector(m, off, dtype=np.complex128, content=b)
+        assert emu.dhqr_solve_c64(h, P(G.ptr), m, n, lda, P(al.ptr), P(bg.ptr)) == 0, emu.dhqr_last_error()
+        assert emu.dhqr_synchronize(h) == 0, emu.dhqr_last_error()
+        assert np.abs(bg.view[:n] - xo).max() <= 1e-10 * np.abs(xo).max(), "x"
+        for g, what in ((G, "A"), (al, "alpha"), (bg, "b")):
+            assert_guards_intact(g, what)
+
+    try:
+        each_layout(m, run, [("control", (0, 0)), ("lda+1", (1, 0)), ("lda+1_off1", (1, 1))])
+    finally:
+        emu.dhqr_destroy(h)
