@@ -232,9 +232,9 @@ class DistributedHouseholderQRStruct:
 
     def __init__(self, A, α=None):
         self.A = A
-        if α is None:  # src:306-309  α = zeros(eltype(A), size(A, 2))
-            n = A.shape[1]
-            α = torch.zeros(n, dtype=A.dtype, device=A.device) if _is_tensor(A) else np.zeros(n, dtype=A.dtype)
+        if α is None:  # src:306-309  α = zeros(eltype(A), size(A, 2)); a batch (batch, m, n) has one α per matrix: (batch, n)
+            shape = tuple(A.shape[:-2]) + (A.shape[-1],)
+            α = torch.zeros(shape, dtype=A.dtype, device=A.device) if _is_tensor(A) else np.zeros(shape, dtype=A.dtype)
         self.α = α
 
     @property
@@ -351,9 +351,133 @@ def solve_householder_(b, H, α):
 def ldiv(H: DistributedHouseholderQRStruct, b):
     """`H \\ b` (src:317-321): least-squares solution of length n; the caller's b is NOT modified
     (the reference copies it into a SharedArray first, src:318)."""
+    if H.A.ndim == 3:
+        return ldiv_batched(H, b)
     if _is_tensor(H.A):
         return solve_householder_(b.clone(), H.A, H.α)
     return solve_householder_(b, H.A, H.α)
+
+
+# ------------------------------------------------------------------------------- batches of small matrices
+def empty_colmajor_batched(batch: int, m: int, n: int, device="cuda"):
+    """uninitialised (batch, m, n) float64 device tensor whose matrices are column-major (stride(1) == 1, lda = m)."""
+    return torch.empty((batch, n, m), dtype=torch.float64, device=device).transpose(1, 2)
+
+
+def rand_colmajor_batched(batch: int, m: int, n: int, seed: int, device="cuda"):
+    """matrix k = rand_colmajor(m, n, seed + k): the shared generator, so the oracle's rand_matrix(m, n, seed + k) is its twin."""
+    A = empty_colmajor_batched(batch, m, n, device)
+    ctx = get_context(A.device.index)
+    ctx.use_torch_stream()
+    L = _lib.lib()
+    for k in range(batch):
+        check(L.dhqr_fill_uniform_f64(ctx.handle, ctypes.c_void_p(A[k].data_ptr()), m, n, m, seed + k, m, 0, NB, 1, 0))
+    return A
+
+
+def _batch_layout(shape, strides):
+    """(lda, strideA) in elements of a (batch, m, n) array whose matrices are column-major, else None"""
+    batch, m, n = shape
+    s0, s1, s2 = strides
+    if m > 1 and s1 != 1:
+        return None
+    lda = s2 if n > 1 else max(m, 1)
+    if lda < max(m, 1):
+        return None
+    need = lda * (n - 1) + m
+    strideA = s0 if batch > 1 else max(need, 1)
+    return (lda, strideA) if strideA >= need else None
+
+
+def _host_rows(v, batch, length, name):
+    """(array, row stride in elements) of a (batch, length) float64 host array with contiguous rows"""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape != (batch, length):
+        raise ValueError(f"{name} must have shape ({batch}, {length})")
+    if (length > 1 and v.strides[1] != v.itemsize) or (batch > 1 and (v.strides[0] % v.itemsize or v.strides[0] < length * v.itemsize)):
+        v = np.ascontiguousarray(v)
+    return v, (v.strides[0] // v.itemsize if batch > 1 else max(length, 1))
+
+
+def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
+    """qr!(A[k]) for every matrix of a (batch, m, n) float64 batch in ONE call (dhqr_factor_batched_f64 /
+    dhqr_qr_batched_f64): one wave per matrix up to 64 x 32, one workgroup per matrix up to the small route's shapes, a
+    serial loop beyond.  A is a CUDA tensor whose matrices are column-major (empty_colmajor_batched) or a numpy array; a
+    host array in another layout is copied to that layout and back.  Mutates A; returns the struct with α of shape (batch, n)."""
+    L = _lib.lib()
+    if A.ndim != 3:
+        raise ValueError("(batch, m, n) array expected")
+    batch, m, n = A.shape
+    if nb is None:
+        nb = 0 if m <= DEFAULT_UNBLOCKED_MAX_ROWS else NB
+    if _is_tensor(A):
+        if A.dtype != torch.float64 or not A.is_cuda:
+            raise TypeError("device path needs a float64 CUDA tensor")
+        lay = _batch_layout(A.shape, A.stride())
+        if lay is None:
+            raise ValueError("matrices of the batch must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
+        H = DistributedHouseholderQRStruct(A)
+        ctx = get_context(A.device.index)
+        ctx.use_torch_stream()
+        check(L.dhqr_factor_batched_f64(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
+                                        ctypes.c_void_p(H.α.data_ptr()), max(n, 1), batch, nb))
+        ctx.synchronize()
+        return H
+    if not isinstance(A, np.ndarray) or A.dtype != np.float64:
+        raise TypeError("float64 numpy array or CUDA tensor expected")
+    lay = None
+    if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
+        lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
+    F = A
+    if lay is None:
+        F = np.empty((batch, n, m)).transpose(0, 2, 1)
+        F[...] = A
+        lay = (max(m, 1), max(m * n, 1))
+    H = DistributedHouseholderQRStruct(A)
+    check(L.dhqr_qr_batched_f64(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+                                H.α.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch, nb))
+    if F is not A:
+        A[...] = F
+    return H
+
+
+def ldiv_batched(H: DistributedHouseholderQRStruct, b):
+    """`H[k] \\ b[k]` for every matrix of a batched factorisation: b (batch, m) -> x (batch, n); b is NOT modified."""
+    L = _lib.lib()
+    A, α = H.A, H.α
+    if A.ndim != 3:
+        raise ValueError("batched factorisation expected")
+    batch, m, n = A.shape
+    if _is_tensor(A):
+        lay = _batch_layout(A.shape, A.stride())
+        if lay is None:
+            raise ValueError("matrices of the batch must be column-major (stride(1) == 1)")
+        if not _is_tensor(b) or b.dtype != torch.float64 or not b.is_cuda or tuple(b.shape) != (batch, m):
+            raise TypeError(f"float64 CUDA tensor of shape ({batch}, {m}) expected")
+        if α.dtype != torch.float64 or tuple(α.shape) != (batch, n) or not α.is_contiguous():
+            raise TypeError(f"α must be a contiguous float64 tensor of shape ({batch}, {n})")
+        w = b.clone(memory_format=torch.contiguous_format)  # src:318 copy of b
+        ctx = get_context(A.device.index)
+        ctx.use_torch_stream()
+        check(L.dhqr_solve_batched_f64(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
+                                       ctypes.c_void_p(α.data_ptr()), max(n, 1), ctypes.c_void_p(w.data_ptr()), max(m, 1), batch))
+        ctx.synchronize()
+        return w[:, :n].clone()
+    lay = None
+    if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
+        lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
+    F = A
+    if lay is None:
+        F = np.empty((batch, n, m)).transpose(0, 2, 1)
+        F[...] = A
+        lay = (max(m, 1), max(m * n, 1))
+    al, sal = _host_rows(α, batch, n, "α")
+    bb, sb = _host_rows(b, batch, m, "b")
+    x = np.empty((batch, n))
+    check(L.dhqr_ldiv_batched_f64(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+                                  al.ctypes.data_as(ctypes.c_void_p), sal, bb.ctypes.data_as(ctypes.c_void_p), sb,
+                                  x.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch))
+    return x
 
 
 def _partialdot_c64(a, b, lo: int, hi: int) -> complex:

@@ -13,6 +13,7 @@
 #include "dhqr_solve.h"
 #include "dhqr_qtb.h"
 #include "dhqr_small.h"
+#include "dhqr_batched.h"
 #include "dhqr_tsqr.h"
 
 static thread_local char g_err[512] = "";
@@ -1130,28 +1131,41 @@ static inline int small_qr_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
 static inline bool small_ldiv_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
   return c->small_route && m <= SML_LDR && n >= 1 && n <= m;
 }
-static int32_t small_qr_launch(dhqr_ctx *c, int fit, const double *Asrc, int64_t lds, double *Adst, int64_t ldd, int64_t m,
-                               int64_t n, double *alpha, unsigned long long *done, unsigned long long epoch) {
+// A batch (dhqr_factor_batched_f64 / dhqr_solve_batched_f64): grid = batch, workgroup k on matrix k (strides in elements).
+struct SmallBatch {
+  int64_t batch = 1, strideA = 0, stride_alpha = 0, strideb = 0;
+};
+static int32_t small_qr_launch_strided(dhqr_ctx *c, int fit, const double *Asrc, int64_t lds, double *Adst, int64_t ldd,
+                                       int64_t m, int64_t n, double *alpha, unsigned long long *done, unsigned long long epoch,
+                                       const SmallBatch &sb) {
+#define DHQR_SMQ(NR_, NQ_, THREADS_, ...)                                                                                 \
+  hipLaunchKernelGGL((k_small_qr_d<NR_, NQ_, __VA_ARGS__>), dim3((unsigned)sb.batch), dim3(THREADS_), 0, c->stream, Asrc, lds, \
+                     Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch, sb.strideA, sb.strideA, sb.stride_alpha)
   // (k_small_qr_d: the reflectors are built by a ninth wave / by another wave than the column's owner, dhqr_small.h)
   if (fit == 0)
-    hipLaunchKernelGGL((k_small_qr_d<8, 4, true>), dim3(1), dim3(SMB_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch);
+    DHQR_SMQ(8, 4, SMB_THREADS, true);
   else if (fit == 1 && c->small_flags)  // (above 128 rows: no barrier in the column loop, LDS flags instead; DHQR_TUNE small_flags=0)
-    hipLaunchKernelGGL((k_small_qr_d<14, 7, false, true>), dim3(1), dim3(SMQ_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch);
+    DHQR_SMQ(14, 7, SMQ_THREADS, false, true);
   else if (fit == 1)
-    hipLaunchKernelGGL((k_small_qr_d<14, 7, false>), dim3(1), dim3(SMQ_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch);
+    DHQR_SMQ(14, 7, SMQ_THREADS, false);
   else if (c->small_flags)
-    hipLaunchKernelGGL((k_small_qr_d<16, 6, false, true>), dim3(1), dim3(SMQ_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch);
+    DHQR_SMQ(16, 6, SMQ_THREADS, false, true);
   else
-    hipLaunchKernelGGL((k_small_qr_d<16, 6, false>), dim3(1), dim3(SMQ_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha, c->small_spin_limit, done, epoch);
+    DHQR_SMQ(16, 6, SMQ_THREADS, false);
+#undef DHQR_SMQ
   LAUNCHCHECK();
   return DHQR_OK;
 }
+static int32_t small_qr_launch(dhqr_ctx *c, int fit, const double *Asrc, int64_t lds, double *Adst, int64_t ldd, int64_t m,
+                               int64_t n, double *alpha, unsigned long long *done, unsigned long long epoch) {
+  return small_qr_launch_strided(c, fit, Asrc, lds, Adst, ldd, m, n, alpha, done, epoch, SmallBatch());
+}
 static int32_t small_ldiv_launch(dhqr_ctx *c, const double *A, int64_t lda, int64_t m, int64_t n, const double *alpha,
                                  const double *bin, double *bout, double *xout, double *Awork, unsigned long long *done = nullptr,
-                                 unsigned long long epoch = 0) {
+                                 unsigned long long epoch = 0, const SmallBatch &sb = SmallBatch()) {
 #define DHQR_SML(RPL_, CH_, AW_)                                                                                            \
-  hipLaunchKernelGGL((k_small_ldiv<RPL_, CH_>), dim3(1), dim3(SML_THREADS), 0, c->stream, A, lda, (int)m, (int)n, alpha, bin, \
-                     bout, xout, AW_, done, epoch)
+  hipLaunchKernelGGL((k_small_ldiv<RPL_, CH_>), dim3((unsigned)sb.batch), dim3(SML_THREADS), 0, c->stream, A, lda, (int)m, (int)n, \
+                     alpha, bin, bout, xout, AW_, done, epoch, sb.strideA, sb.stride_alpha, sb.strideb)
   // (<= 128 rows: 64-column chunks straight from the caller's memory, no device copy of the factor)
   if (m <= 64) DHQR_SML(1, 64, (double *)nullptr);
   else if (m <= 128) DHQR_SML(2, 64, (double *)nullptr);
@@ -1327,6 +1341,7 @@ int32_t dhqr_create(dhqr_ctx **out, int32_t device) {
     if (const char *e = getenv("DHQR_RANKK_PIPE")) c->rankk_pipe = std::min(2, std::max(0, atoi(e)));
     { long long v; if (tune_get("tn_min_tiles", &v)) c->tn_model_min_tiles = (int)v; }
     { long long v; if (tune_get("small_flags", &v)) c->small_flags = v != 0; }
+    { long long v; if (tune_get("batched_wave", &v)) c->batched_wave = v != 0; }
     { long long v; if (tune_get("short_panel_small", &v)) c->short_panel_small = v != 0; }
     { long long v; if (tune_get("partial_unblocked", &v)) c->partial_unblocked = v != 0; }
     { long long v; if (tune_get("partial_unblocked_max_rows", &v)) c->partial_unblocked_max_rows = v; }
@@ -1394,7 +1409,7 @@ int32_t dhqr_destroy(dhqr_ctx *c) {
     c->hio = nullptr;
   }
   Buf *bufs[] = {&c->vbuf, &c->vt, &c->vts, &c->ws[0].w1, &c->ws[0].w1r, &c->ws[0].w2, &c->ws[1].w1,
-                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp};
+                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp, &c->batch_dev};
   for (Buf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (auto &e : c->evs) {
@@ -1472,7 +1487,7 @@ int32_t dhqr_trim(dhqr_ctx *c) {
   HIPCHECK(hipStreamSynchronize(c->stream));
   HIPCHECK(hipDeviceSynchronize());  // the lane, side, comm and copy streams of this context
   Buf *bs[] = {&c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->vts, &c->tsq, &c->zsolve_lo,
-               &c->small_dev, &c->sv_bkp};
+               &c->small_dev, &c->sv_bkp, &c->batch_dev};
   c->retry.valid = false;
   if (c->small_pin) {
     (void)hipHostFree(c->small_pin);
@@ -1965,6 +1980,175 @@ int32_t dhqr_ldiv_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
   int32_t rc = body();
   (void)hipStreamSynchronize(c->stream);
   if (c->hio) (void)hio_drain(*c->hio);
+  return rc;
+}
+
+// ---- batches of small matrices (dhqr.h: dhqr_factor_batched_f64 ...) ------------------------------------------------
+// Tiers by shape: one wave per matrix (dhqr_batched.h) | the single-workgroup kernels of dhqr_small.h with grid = batch, in
+// their barrier form | a host loop over the single-matrix drivers.
+static int32_t check_batch(const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
+                           int64_t stride_alpha, int64_t batch) {
+  CHECK(check_mat(A, m, n, lda, true));
+  if (!alpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  if (strideA < lda * (n - 1) + m)
+    return set_err(DHQR_EINVAL, "strideA %lld < lda*(n-1)+m = %lld", (long long)strideA, (long long)(lda * (n - 1) + m));
+  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
+  if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
+  return DHQR_OK;
+}
+static inline bool batched_wave_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
+  return c->small_route && c->batched_wave && m <= BQW_MAX_M && n <= BQW_MAX_N && n >= 1 && m >= n;
+}
+
+int32_t dhqr_factor_batched_f64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
+                                int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  if (nb != 0 && nb != DHQR_NB)
+    return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
+  const bool wave = batched_wave_fit(c, m, n);
+  const int fit = small_qr_fit(c, m, n);
+  if (!wave && fit < 0) {  // serial: one single-matrix factorisation after the other
+    // (and synchronised after each: the error word of the drivers' bounded waits belongs to one call at a time, dhqr.h)
+    for (int64_t k = 0; k < batch; ++k) {
+      CHECK(dhqr_factor_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, nb));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  c->tc_valid = false;  // whatever was kept for one of these matrices is gone
+  c->retry.valid = false;
+  CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
+  if (wave) {
+    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+    if (n <= 8)
+      hipLaunchKernelGGL((k_batched_qr_wave<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    else if (n <= 16)
+      hipLaunchKernelGGL((k_batched_qr_wave<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    else
+      hipLaunchKernelGGL((k_batched_qr_wave<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    LAUNCHCHECK();
+  } else {
+    // the barrier form for every fit: with a batch in flight the compute units are full either way, and the barrier form
+    // has no bounded wait that could give up (same bits as the flag form)
+    SmallBatch sb;
+    sb.batch = batch;
+    sb.strideA = strideA;
+    sb.stride_alpha = stride_alpha;
+    const int keep = c->small_flags;
+    c->small_flags = 0;
+    const int32_t rc = small_qr_launch_strided(c, fit, dA, lda, dA, lda, m, n, dalpha, nullptr, 0, sb);
+    c->small_flags = keep;
+    CHECK(rc);
+  }
+  if (c->profiling)
+    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 16.0 * (double)(m - j) * (double)(n - j - 1);
+  return prof_end(c);
+}
+
+int32_t dhqr_solve_batched_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const double *dalpha, int64_t stride_alpha, double *db, int64_t strideb, int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  if (!db) return set_err(DHQR_EINVAL, "null b pointer");
+  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
+  const bool wave = batched_wave_fit(c, m, n);
+  if (!wave && !small_ldiv_fit(c, m, n)) {
+    for (int64_t k = 0; k < batch; ++k) {  // (a solve's repetition, pipe_error_check, knows the last solve only)
+      CHECK(dhqr_solve_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, db + k * strideb));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  CHECK(prof_begin(c, CAT_SOLVE));
+  if (wave) {
+    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+    if (n <= 8)
+      hipLaunchKernelGGL((k_batched_ldiv_wave<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    else if (n <= 16)
+      hipLaunchKernelGGL((k_batched_ldiv_wave<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    else
+      hipLaunchKernelGGL((k_batched_ldiv_wave<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    LAUNCHCHECK();
+  } else {
+    SmallBatch sb;
+    sb.batch = batch;
+    sb.strideA = strideA;
+    sb.stride_alpha = stride_alpha;
+    sb.strideb = strideb;
+    CHECK(small_ldiv_launch(c, dA, lda, m, n, dalpha, db, db, nullptr, nullptr, nullptr, 0, sb));  // (the factor is in HBM: no Awork)
+  }
+  return prof_end(c);
+}
+
+// host <-> device copies of `batch` blocks of rows x cols doubles: block k at h + k hstride (leading dimension hld) and at
+// d + k rows cols (packed)
+static int32_t batch_copy(dhqr_ctx *c, double *d, const double *h, int64_t rows, int64_t cols, int64_t hld, int64_t hstride,
+                          int64_t batch, bool up) {
+  auto copy2d = [&](double *dp, const double *hp, int64_t dpitch, int64_t hpitch, int64_t width, int64_t height) -> int32_t {
+    if (up)
+      HIPCHECK(hipMemcpy2DAsync(dp, dpitch * sizeof(double), hp, hpitch * sizeof(double), width * sizeof(double), height,
+                                hipMemcpyHostToDevice, c->stream));
+    else
+      HIPCHECK(hipMemcpy2DAsync(const_cast<double *>(hp), hpitch * sizeof(double), dp, dpitch * sizeof(double),
+                                width * sizeof(double), height, hipMemcpyDeviceToHost, c->stream));
+    return DHQR_OK;
+  };
+  if (hld == rows || cols == 1) return copy2d(d, h, rows * cols, hstride, rows * cols, batch);  // every block contiguous
+  if (hstride == hld * cols) return copy2d(d, h, rows, hld, rows, cols * batch);               // one column pitch throughout
+  for (int64_t k = 0; k < batch; ++k) CHECK(copy2d(d + k * rows * cols, h + k * hstride, rows, hld, rows, cols));
+  return DHQR_OK;
+}
+
+int32_t dhqr_qr_batched_f64(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
+                            int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  if (nb != 0 && nb != DHQR_NB)
+    return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->batch_dev, na + nal));
+  double *dA = c->batch_dev.p, *dal = dA + na;
+  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
+  int32_t rc = dhqr_factor_batched_f64(c, dA, m, n, m, m * n, dal, n, batch, nb);
+  if (rc == DHQR_OK) rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, false);
+  if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, false);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);
+  return rc;
+}
+
+int32_t dhqr_ldiv_batched_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
+                              int64_t stridex, int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  if (!hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
+  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
+  if (stridex < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)stridex, (long long)n);
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->batch_dev, na + nal + (size_t)m * (size_t)batch));
+  double *dA = c->batch_dev.p, *dal = dA + na, *db = dal + nal;
+  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
+  CHECK(batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
+  CHECK(batch_copy(c, db, hb, m, 1, m, strideb, batch, true));  // src:318 copy of b
+  int32_t rc = dhqr_solve_batched_f64(c, dA, m, n, m, m * n, dal, n, db, m, batch);
+  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);  // (the serial tier's solves may have been repeated: dhqr.h)
+  if (rc == DHQR_OK)  // src:320: x_k = the first n entries of b_k
+    HIPCHECK(hipMemcpy2DAsync(hx, stridex * sizeof(double), db, m * sizeof(double), n * sizeof(double), batch,
+                              hipMemcpyDeviceToHost, c->stream));
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
   return rc;
 }
 

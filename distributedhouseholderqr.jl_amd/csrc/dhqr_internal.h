@@ -137,6 +137,8 @@ struct dhqr_ctx {
   size_t small_pin_cap = 0;     // write it across PCIe themselves (no hipMemcpy on the path); doubles
   Buf small_dev;                // device copy of a host factor inside k_small_ldiv (256 x 256)
   unsigned long long small_epoch = 0;  // launches that signalled their end through the pinned word behind small_pin
+  Buf batch_dev;                // device copy of the batch (matrices | alphas | right-hand sides) of dhqr_qr_batched_f64 / dhqr_ldiv_batched_f64
+  int batched_wave = 1;         // batches of matrices of at most 64 x 32: one wave per matrix (dhqr_batched.h; DHQR_TUNE batched_wave=0: the one-CU kernels)
   bool coop = false;     // the device runs cooperative (all-resident) launches: false on the CPU emulator
   Buf host_mat;          // device copy of the caller's HOST matrix (+ alpha) of dhqr_qr_f64, kept between calls
   int pair = 1;                  // 1: wide updates apply two panels per pass (DHQR_PAIR=0 disables)

@@ -212,7 +212,12 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
                                                                                    int64_t ldd, int m, int n,
                                                                                    double *__restrict__ alpha, int spin_limit,
                                                                                    unsigned long long *done,
-                                                                                   unsigned long long epoch) {
+                                                                                   unsigned long long epoch, int64_t strideS,
+                                                                                   int64_t strideD, int64_t stride_alpha) {
+  // a batch (dhqr_factor_batched_f64): workgroup k factors matrix k; a single matrix is launched with one workgroup
+  Asrc += (int64_t)blockIdx.x * strideS;
+  Adst += (int64_t)blockIdx.x * strideD;
+  alpha += (int64_t)blockIdx.x * stride_alpha;
   constexpr int RBL = (16 * NR + 63) / 64;  // rows of a column per lane of the builder
   constexpr int NT = EXTRA ? SMB_THREADS : SMQ_THREADS;
   constexpr int NBUF = FLAGS ? 8 : 2, BM = NBUF - 1;  // reflector / column buffers (by column index)
@@ -431,7 +436,13 @@ template <int RPL, int CH>  // RPL: rows of b per lane of the solving wave, m <=
 __global__ __launch_bounds__(SML_THREADS) void k_small_ldiv(const double *__restrict__ A, int64_t lda, int m, int n,
                                                             const double *__restrict__ alpha, const double *bin, double *bout,
                                                             double *xout, double *__restrict__ Awork, unsigned long long *done,
-                                                            unsigned long long epoch) {
+                                                            unsigned long long epoch, int64_t strideA,
+                                                            int64_t stride_alpha, int64_t strideb) {
+  // a batch (dhqr_solve_batched_f64; xout, Awork and done are nullptr there): workgroup k solves with factor k and b_k
+  A += (int64_t)blockIdx.x * strideA;
+  alpha += (int64_t)blockIdx.x * stride_alpha;
+  bin += (int64_t)blockIdx.x * strideb;
+  bout += (int64_t)blockIdx.x * strideb;
   constexpr int LDR = 64 * RPL;  // rows of a staged column
   __shared__ double buf[2][CH][LDR];
   __shared__ double als[2][CH];

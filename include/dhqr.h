@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define DHQR_VERSION 500 /* 0.5.0: round 6 (dhqr_set_small_route added; nothing else changed) */
+#define DHQR_VERSION 500 /* 0.5.0: round 6 (dhqr_set_small_route added; nothing else changed); since then added, nothing changed:
+                          * dhqr_factor_batched_f64, dhqr_solve_batched_f64, dhqr_qr_batched_f64, dhqr_ldiv_batched_f64 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -194,6 +195,42 @@ int32_t dhqr_backsub_block_f64(dhqr_ctx *ctx, const double *dAcols, int64_t lda,
  * reference copies b into a SharedArray first); writes hx[0:n].  Synchronous. */
 int32_t dhqr_ldiv_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda,
                       const double *halpha, const double *hb, double *hx);
+
+/* ------------------------------------------------------------------ batches of small matrices
+ * `batch` independent problems in one call: the reference's `qr!(A_k)` and `qr!(A_k) \ b_k` repeated for k = 0 .. batch-1,
+ * every matrix with its own factor and its own single right-hand side.  Strided layout: matrix k (m x n, column-major,
+ * leading dimension lda) starts at A + k*strideA, its alpha at alpha + k*stride_alpha, its b at b + k*strideb, its x at
+ * x + k*stridex (strides in elements).  The factor format of every matrix is the single-matrix one (top of this file).
+ * Float64 only.
+ *   dhqr_factor_batched_f64  device-resident, in place, asynchronous on the ctx stream (first two tiers).
+ *   dhqr_solve_batched_f64   device-resident: db_k (m) <- [x_k; tail of Q'b_k]; asynchronous (first two tiers).
+ *   dhqr_qr_batched_f64      host in / host out; synchronous.  The device copy of the batch stays in the context between
+ *                            calls; dhqr_trim releases it.  On an error return hA is undefined.
+ *   dhqr_ldiv_batched_f64    host in / host out `H_k \ b_k`; hb is not modified; synchronous.
+ * Routes by shape, in this order:
+ *   m <= 64 and n <= 32      ONE launch, one WAVE per matrix and four matrices per workgroup (csrc/dhqr_batched.h): the
+ *                            reference's column-by-column algorithm with row l of the matrix in lane l; the solve carries b
+ *                            in double-double.
+ *   the shapes of dhqr_set_small_route (factor: m <= 128 and n <= 128, m <= 224 and n <= 224, m <= 256 and n <= 192;
+ *   solve: m <= 256)         ONE launch of the single-workgroup kernels with grid = batch, workgroup k on matrix k, always in
+ *                            their barrier form: results BIT-IDENTICAL to dhqr_factor_f64 / dhqr_solve_f64 of matrix k alone
+ *                            with the small route on.
+ *   everything else          a host loop over dhqr_factor_f64 / dhqr_solve_f64 with the caller's nb: serial, and
+ *                            synchronised after every matrix; the results of the single calls.
+ * dhqr_set_small_route(ctx, 0) (or DHQR_SMALL=0) sends every shape to the loop.  nb (0 or DHQR_NB) is ignored on the first
+ * two routes.  With profiling on, a batched factor on the first two routes counts ONE n_rank1 group (time in ms_rank1) and
+ * a batched solve one n_solve (ms_solve), whatever the batch.
+ * batch == 0 or n == 0: no-op, DHQR_OK.  DHQR_EINVAL: batch < 0, m < n, lda < m, strideA < lda*(n-1) + m (the last column
+ * of a matrix may be short of lda), stride_alpha < n, strideb < m, stridex < n, null pointers. */
+int32_t dhqr_factor_batched_f64(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                double *dalpha, int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_solve_batched_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const double *dalpha, int64_t stride_alpha, double *db, int64_t strideb, int64_t batch);
+int32_t dhqr_qr_batched_f64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                            double *halpha, int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_ldiv_batched_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
+                              int64_t stridex, int64_t batch);
 
 /* KAT hook mirroring partialdot(a, b, lo:hi, Float64) (src:42-49; test/partialdot.jl:18):
  * sum_{i=lo}^{hi-1} da[i]*db[i] (0-based, hi exclusive) reduced on the device with the same

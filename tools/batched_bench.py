@@ -1,0 +1,127 @@
+"""Throughput of the batched qr! + `\\` (dhqr_factor_batched_f64 + dhqr_solve_batched_f64) against what a caller had before:
+a loop of `batch` single calls (dhqr_factor_f64 with the small route on, then dhqr_solve_f64) on the same resident data.
+
+usage: python tools/batched_bench.py [--out FILE]          every point, each in a child process under `timeout -k 10`
+       python tools/batched_bench.py --point M N BATCH     one point (what the children run)
+
+Per point: 3 warm-up and 10 timed repetitions of (restore the inputs, synchronise, START, calls, synchronise, STOP) on the
+host clock -- a caller's view, launch costs included; median and min-max of matrices per second; the ratio batched / looped
+of the medians.  Shapes of at most 64 x 32 are also run with DHQR_TUNE batched_wave=0 (one workgroup per matrix instead of
+one wave per matrix), which is what the wave kernels have to beat.  The run stops at the first point that fails."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(12, 6), (16, 8), (32, 16), (64, 32), (110, 100), (220, 200)]
+BATCHES = [64, 1024, 16384]
+WARMUP, REPS = 3, 10
+
+
+def point(m, n, batch):
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as g
+    pkg = g.import_package()
+    batch = min(batch, (4 << 30) // (m * n * 8) - 1)  # the batch stays under 4 GiB
+    A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0")
+    b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    A, b = A0.clone(), b0.clone()
+    al = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    L = pkg._lib.lib()
+    P = ctypes.c_void_p
+    pa, pal, pb = A.data_ptr(), al.data_ptr(), b.data_ptr()
+    os.environ["DHQR_SMALL"] = "1"
+
+    def measure(ctx, fn):
+        rates = []
+        for r in range(WARMUP + REPS):
+            A.copy_(A0)
+            b.copy_(b0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(ctx.handle)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(batch / dt)
+        return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
+
+    def batched(h):
+        pkg._lib.check(L.dhqr_factor_batched_f64(h, P(pa), m, n, m, m * n, P(pal), n, batch, 0))
+        pkg._lib.check(L.dhqr_solve_batched_f64(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), m, batch))
+
+    def looped(h):
+        for k in range(batch):
+            ak, alk = P(pa + 8 * k * m * n), P(pal + 8 * k * n)
+            pkg._lib.check(L.dhqr_factor_f64(h, ak, m, n, m, alk, 0))
+            pkg._lib.check(L.dhqr_solve_f64(h, ak, m, n, m, alk, P(pb + 8 * k * m)))
+
+    out = {"m": m, "n": n, "batch": batch}
+    ctx = pkg.Context(0)
+    out["batched"] = measure(ctx, batched)
+    x = b[:, :n].clone()
+    out["looped"] = measure(ctx, looped)
+    ctx.close()
+    if m <= 64 and n <= 32:
+        assert ((x - b[:, :n]).abs().amax(dim=1) <= 1e-9 * x.abs().amax(dim=1)).all(), "batched and looped solutions differ"
+        os.environ["DHQR_TUNE"] = "batched_wave=0"
+        ctx = pkg.Context(0)
+        out["batched_one_cu"] = measure(ctx, batched)
+        ctx.close()
+    else:
+        assert torch.equal(x, b[:, :n]), "the one-workgroup tier must give the single calls' bits"
+    print("POINT " + json.dumps(out), flush=True)
+
+
+def fmt(r):
+    return f"{r['median']:12.0f} ({r['min']:.0f} .. {r['max']:.0f})"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--point", nargs=3, type=int)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
+    a = ap.parse_args()
+    if a.point:
+        point(*a.point)
+        return 0
+    lines = ["# tools/batched_bench.py: qr! + \\ of `batch` matrices, matrices per second, median (min .. max) of 10 repetitions",
+             "# batched = one dhqr_factor_batched_f64 + one dhqr_solve_batched_f64; looped = batch x (dhqr_factor_f64 + dhqr_solve_f64), small route on",
+             "# one-CU = the batched calls with DHQR_TUNE batched_wave=0 (one workgroup per matrix) on the wave tier's shapes"]
+    print("\n".join(lines), flush=True)
+    for (m, n) in SHAPES:
+        for batch in BATCHES:
+            p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
+                                str(m), str(n), str(batch)], capture_output=True, text=True)
+            row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
+            if p.returncode != 0 or not row:
+                lines.append(f"{m}x{n} batch {batch}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
+                print(lines[-1], flush=True)
+                break
+            r = json.loads(row[0][6:])
+            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} | batched {fmt(r['batched'])} | looped {fmt(r['looped'])} | "
+                   f"batched/looped {r['batched']['median'] / r['looped']['median']:8.1f}x")
+            if "batched_one_cu" in r:
+                txt += (f" | one-CU {fmt(r['batched_one_cu'])} | wave/one-CU "
+                        f"{r['batched']['median'] / r['batched_one_cu']['median']:6.1f}x")
+            lines.append(txt)
+            print(txt, flush=True)
+        else:
+            continue
+        break
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
