@@ -137,6 +137,31 @@ def _is_complex(x) -> bool:
     return isinstance(x, np.ndarray) and x.dtype == np.complex128
 
 
+def _is_f32(x) -> bool:
+    if _is_tensor(x):
+        return x.dtype == torch.float32
+    return isinstance(x, np.ndarray) and x.dtype == np.float32
+
+
+def _same_dtype(A, v, name):
+    """Float32 and Float64 methods are separate (the reference dispatches on the element type): a float32 matrix with a
+    float64 vector, or the reverse, is a TypeError, never a silent conversion -- also on the Float64 paths, which used to
+    convert a float32 host `b` quietly"""
+    dt = getattr(v, "dtype", None)
+    real = (np.float32, np.float64) if torch is None else (torch.float32, torch.float64, np.float32, np.float64)
+    if dt is not None and any(dt == t for t in real) and _is_f32(A) != _is_f32(v):
+        raise TypeError(f"{name} is {dt} but the matrix is {A.dtype}: convert one of them explicitly")
+
+
+def _resolve_dtype(dtype):
+    """torch dtype of a `dtype` argument (None = float64, today's behaviour); float32 and float64 in torch's or numpy's spelling"""
+    if dtype is None or dtype in (torch.float64, np.float64, "float64"):
+        return torch.float64
+    if dtype in (torch.float32, np.float32, "float32"):
+        return torch.float32
+    raise TypeError(f"dtype must be float64 or float32, got {dtype!r}")
+
+
 def _host_ld(F) -> int:
     """leading dimension (in elements) of a column-major host matrix; numpy's relaxed strides report an
     arbitrary stride for a single column, where the reference's Matrix simply has ld = m"""
@@ -189,16 +214,21 @@ def _dev_vector(v, length=None, dtype=None):
     return ctypes.c_void_p(v.data_ptr())
 
 
-def empty_colmajor(m: int, n: int, device="cuda"):
-    """uninitialised m x n float64 device matrix in column-major layout (lda = m)."""
-    return torch.empty((n, m), dtype=torch.float64, device=device).t()
+def empty_colmajor(m: int, n: int, device="cuda", dtype=None):
+    """uninitialised m x n float64 (or dtype=float32) device matrix in column-major layout (lda = m)."""
+    return torch.empty((n, m), dtype=_resolve_dtype(dtype), device=device).t()
 
 
 def rand_colmajor(m: int, n: int, seed: int, device="cuda", *, global_m=None, row0=0, colblock=NB,
-                  nranks=1, rank=0):
+                  nranks=1, rank=0, dtype=None):
     """Device-side synthetic input: A[i,j] = u01(seed, gi + gj*global_m), the generator shared with
     oracle/ (stands in for rand(T,m,n), test/runtests.jl:45).  With nranks > 1 fills the LOCAL
-    block of a block-cyclic column layout."""
+    block of a block-cyclic column layout.  dtype=float32: the same Float64 values, rounded."""
+    if _resolve_dtype(dtype) == torch.float32:
+        A64 = rand_colmajor(m, n, seed, device, global_m=global_m, row0=row0, colblock=colblock, nranks=nranks, rank=rank)
+        A = empty_colmajor(m, n, device, torch.float32)
+        A.copy_(A64)
+        return A
     A = empty_colmajor(m, n, device)
     ctx = get_context(A.device.index)
     ctx.use_torch_stream()
@@ -269,6 +299,30 @@ def _householder_c64(A, α, nb=0):
     return A, α
 
 
+def _householder_f32(A, α, nb):
+    """Float32 method of householder! (dhqr_factor_f32 / dhqr_qr_f32): native kernels up to 64 x 32, promoted beyond"""
+    L = _lib.lib()
+    _same_dtype(A, α, "α")
+    if _is_tensor(A):
+        ptr, m, n, lda, dev = _dev_matrix(A, torch.float32)
+        ctx = get_context(dev)
+        ctx.use_torch_stream()
+        check(L.dhqr_factor_f32(ctx.handle, ptr, m, n, lda, _dev_vector(α, n, torch.float32), nb))
+        ctx.synchronize()
+        return A, α
+    if A.ndim != 2:
+        raise TypeError("float32 numpy matrix or CUDA tensor expected")
+    if not isinstance(α, np.ndarray) or α.dtype != np.float32 or α.size < A.shape[1] or not α.flags.c_contiguous:
+        raise TypeError("α must be a contiguous float32 numpy vector of length n")
+    m, n = A.shape
+    F = A if A.flags.f_contiguous else np.asfortranarray(A)
+    check(L.dhqr_qr_f32(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, _host_ld(F),
+                        α.ctypes.data_as(ctypes.c_void_p), nb))
+    if F is not A:
+        A[...] = F
+    return A, α
+
+
 def householder_(A, α, nb: Optional[int] = None):
     """householder!(A, α) (src:113): factor A in place, fill α. nb=0 -> unblocked rank-1 path
     (the reference's algorithm verbatim), nb=128 -> blocked MFMA path (the Float64 default).
@@ -277,7 +331,10 @@ def householder_(A, α, nb: Optional[int] = None):
     nb = _resolve_nb(A, nb)
     if _is_complex(A):
         return _householder_c64(A, α, nb)
+    if _is_f32(A):
+        return _householder_f32(A, α, nb)
     if _is_tensor(A):
+        _same_dtype(A, α, "α")
         ptr, m, n, lda, dev = _dev_matrix(A)
         ctx = get_context(dev)
         ctx.use_torch_stream()
@@ -330,6 +387,24 @@ def solve_householder_(b, H, α):
                               np.ascontiguousarray(α, dtype=np.complex128).ctypes.data_as(ctypes.c_void_p),
                               bb.ctypes.data_as(ctypes.c_void_p), x.ctypes.data_as(ctypes.c_void_p)))
         return x
+    _same_dtype(H, α, "α")
+    _same_dtype(H, b, "b")
+    if _is_f32(H):
+        if _is_tensor(H):
+            ptr, m, n, lda, dev = _dev_matrix(H, torch.float32)
+            ctx = get_context(dev)
+            ctx.use_torch_stream()
+            check(L.dhqr_solve_f32(ctx.handle, ptr, m, n, lda, _dev_vector(α, n, torch.float32), _dev_vector(b, m, torch.float32)))
+            ctx.synchronize()
+            return b[:n].clone()
+        m, n = H.shape
+        F = H if H.flags.f_contiguous else np.asfortranarray(H)
+        x = np.empty(n, dtype=np.float32)
+        bb = np.ascontiguousarray(b, dtype=np.float32)
+        check(L.dhqr_ldiv_f32(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, _host_ld(F),
+                              np.ascontiguousarray(α, dtype=np.float32).ctypes.data_as(ctypes.c_void_p),
+                              bb.ctypes.data_as(ctypes.c_void_p), x.ctypes.data_as(ctypes.c_void_p)))
+        return x
     if _is_tensor(H):
         ptr, m, n, lda, dev = _dev_matrix(H)
         ctx = get_context(dev)
@@ -359,13 +434,18 @@ def ldiv(H: DistributedHouseholderQRStruct, b):
 
 
 # ------------------------------------------------------------------------------- batches of small matrices
-def empty_colmajor_batched(batch: int, m: int, n: int, device="cuda"):
-    """uninitialised (batch, m, n) float64 device tensor whose matrices are column-major (stride(1) == 1, lda = m)."""
-    return torch.empty((batch, n, m), dtype=torch.float64, device=device).transpose(1, 2)
+def empty_colmajor_batched(batch: int, m: int, n: int, device="cuda", dtype=None):
+    """uninitialised (batch, m, n) float64 (or dtype=float32) device tensor whose matrices are column-major (stride(1) == 1, lda = m)."""
+    return torch.empty((batch, n, m), dtype=_resolve_dtype(dtype), device=device).transpose(1, 2)
 
 
-def rand_colmajor_batched(batch: int, m: int, n: int, seed: int, device="cuda"):
-    """matrix k = rand_colmajor(m, n, seed + k): the shared generator, so the oracle's rand_matrix(m, n, seed + k) is its twin."""
+def rand_colmajor_batched(batch: int, m: int, n: int, seed: int, device="cuda", dtype=None):
+    """matrix k = rand_colmajor(m, n, seed + k): the shared generator, so the oracle's rand_matrix(m, n, seed + k) is its twin.
+    dtype=float32: the same Float64 values, rounded."""
+    if _resolve_dtype(dtype) == torch.float32:
+        A = empty_colmajor_batched(batch, m, n, device, torch.float32)
+        A.copy_(rand_colmajor_batched(batch, m, n, seed, device))
+        return A
     A = empty_colmajor_batched(batch, m, n, device)
     ctx = get_context(A.device.index)
     ctx.use_torch_stream()
@@ -389,9 +469,9 @@ def _batch_layout(shape, strides):
     return (lda, strideA) if strideA >= need else None
 
 
-def _host_rows(v, batch, length, name):
-    """(array, row stride in elements) of a (batch, length) float64 host array with contiguous rows"""
-    v = np.asarray(v, dtype=np.float64)
+def _host_rows(v, batch, length, name, dtype=np.float64):
+    """(array, row stride in elements) of a (batch, length) float64 (or `dtype`) host array with contiguous rows"""
+    v = np.asarray(v, dtype=dtype)
     if v.shape != (batch, length):
         raise ValueError(f"{name} must have shape ({batch}, {length})")
     if (length > 1 and v.strides[1] != v.itemsize) or (batch > 1 and (v.strides[0] % v.itemsize or v.strides[0] < length * v.itemsize)):
@@ -410,31 +490,33 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
     batch, m, n = A.shape
     if nb is None:
         nb = 0 if m <= DEFAULT_UNBLOCKED_MAX_ROWS else NB
+    f32 = _is_f32(A)
+    factor, qr = (L.dhqr_factor_batched_f32, L.dhqr_qr_batched_f32) if f32 else (L.dhqr_factor_batched_f64, L.dhqr_qr_batched_f64)
     if _is_tensor(A):
-        if A.dtype != torch.float64 or not A.is_cuda:
-            raise TypeError("device path needs a float64 CUDA tensor")
+        if A.dtype not in (torch.float64, torch.float32) or not A.is_cuda:
+            raise TypeError("device path needs a float64 or float32 CUDA tensor")
         lay = _batch_layout(A.shape, A.stride())
         if lay is None:
             raise ValueError("matrices of the batch must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
         H = DistributedHouseholderQRStruct(A)
         ctx = get_context(A.device.index)
         ctx.use_torch_stream()
-        check(L.dhqr_factor_batched_f64(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
+        check(factor(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
                                         ctypes.c_void_p(H.α.data_ptr()), max(n, 1), batch, nb))
         ctx.synchronize()
         return H
-    if not isinstance(A, np.ndarray) or A.dtype != np.float64:
-        raise TypeError("float64 numpy array or CUDA tensor expected")
+    if not isinstance(A, np.ndarray) or A.dtype not in (np.float64, np.float32):
+        raise TypeError("float64 or float32 numpy array or CUDA tensor expected")
     lay = None
     if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
         lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
     F = A
     if lay is None:
-        F = np.empty((batch, n, m)).transpose(0, 2, 1)
+        F = np.empty((batch, n, m), dtype=A.dtype).transpose(0, 2, 1)
         F[...] = A
         lay = (max(m, 1), max(m * n, 1))
     H = DistributedHouseholderQRStruct(A)
-    check(L.dhqr_qr_batched_f64(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+    check(qr(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
                                 H.α.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch, nb))
     if F is not A:
         A[...] = F
@@ -448,18 +530,22 @@ def ldiv_batched(H: DistributedHouseholderQRStruct, b):
     if A.ndim != 3:
         raise ValueError("batched factorisation expected")
     batch, m, n = A.shape
+    f32 = _is_f32(A)
+    _same_dtype(A, α, "α")
+    _same_dtype(A, b, "b")
+    solve, ldiv_ = (L.dhqr_solve_batched_f32, L.dhqr_ldiv_batched_f32) if f32 else (L.dhqr_solve_batched_f64, L.dhqr_ldiv_batched_f64)
     if _is_tensor(A):
         lay = _batch_layout(A.shape, A.stride())
         if lay is None:
             raise ValueError("matrices of the batch must be column-major (stride(1) == 1)")
-        if not _is_tensor(b) or b.dtype != torch.float64 or not b.is_cuda or tuple(b.shape) != (batch, m):
-            raise TypeError(f"float64 CUDA tensor of shape ({batch}, {m}) expected")
-        if α.dtype != torch.float64 or tuple(α.shape) != (batch, n) or not α.is_contiguous():
-            raise TypeError(f"α must be a contiguous float64 tensor of shape ({batch}, {n})")
+        if not _is_tensor(b) or b.dtype != A.dtype or not b.is_cuda or tuple(b.shape) != (batch, m):
+            raise TypeError(f"{A.dtype} CUDA tensor of shape ({batch}, {m}) expected")
+        if α.dtype != A.dtype or tuple(α.shape) != (batch, n) or not α.is_contiguous():
+            raise TypeError(f"α must be a contiguous {A.dtype} tensor of shape ({batch}, {n})")
         w = b.clone(memory_format=torch.contiguous_format)  # src:318 copy of b
         ctx = get_context(A.device.index)
         ctx.use_torch_stream()
-        check(L.dhqr_solve_batched_f64(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
+        check(solve(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1],
                                        ctypes.c_void_p(α.data_ptr()), max(n, 1), ctypes.c_void_p(w.data_ptr()), max(m, 1), batch))
         ctx.synchronize()
         return w[:, :n].clone()
@@ -468,13 +554,13 @@ def ldiv_batched(H: DistributedHouseholderQRStruct, b):
         lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
     F = A
     if lay is None:
-        F = np.empty((batch, n, m)).transpose(0, 2, 1)
+        F = np.empty((batch, n, m), dtype=A.dtype).transpose(0, 2, 1)
         F[...] = A
         lay = (max(m, 1), max(m * n, 1))
-    al, sal = _host_rows(α, batch, n, "α")
-    bb, sb = _host_rows(b, batch, m, "b")
-    x = np.empty((batch, n))
-    check(L.dhqr_ldiv_batched_f64(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+    al, sal = _host_rows(α, batch, n, "α", A.dtype)
+    bb, sb = _host_rows(b, batch, m, "b", A.dtype)
+    x = np.empty((batch, n), dtype=A.dtype)
+    check(ldiv_(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
                                   al.ctypes.data_as(ctypes.c_void_p), sal, bb.ctypes.data_as(ctypes.c_void_p), sb,
                                   x.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch))
     return x

@@ -14,6 +14,7 @@
 #include "dhqr_qtb.h"
 #include "dhqr_small.h"
 #include "dhqr_batched.h"
+#include "dhqr_f32.h"
 #include "dhqr_tsqr.h"
 
 static thread_local char g_err[512] = "";
@@ -1409,7 +1410,7 @@ int32_t dhqr_destroy(dhqr_ctx *c) {
     c->hio = nullptr;
   }
   Buf *bufs[] = {&c->vbuf, &c->vt, &c->vts, &c->ws[0].w1, &c->ws[0].w1r, &c->ws[0].w2, &c->ws[1].w1,
-                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp, &c->batch_dev};
+                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp, &c->batch_dev, &c->f32_ws, &c->f32_dev};
   for (Buf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (auto &e : c->evs) {
@@ -1487,7 +1488,7 @@ int32_t dhqr_trim(dhqr_ctx *c) {
   HIPCHECK(hipStreamSynchronize(c->stream));
   HIPCHECK(hipDeviceSynchronize());  // the lane, side, comm and copy streams of this context
   Buf *bs[] = {&c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->vts, &c->tsq, &c->zsolve_lo,
-               &c->small_dev, &c->sv_bkp, &c->batch_dev};
+               &c->small_dev, &c->sv_bkp, &c->batch_dev, &c->f32_ws, &c->f32_dev};
   c->retry.valid = false;
   if (c->small_pin) {
     (void)hipHostFree(c->small_pin);
@@ -2150,6 +2151,233 @@ int32_t dhqr_ldiv_batched_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t 
                               hipMemcpyDeviceToHost, c->stream));
   if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
   return rc;
+}
+
+// ---- Float32 (dhqr.h: dhqr_factor_f32 ...) -----------------------------------------------------------------------------
+// Two tiers: m <= 64 and n <= 32 with the small route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single
+// matrix is a batch of 1) --, everything else PROMOTED: widened into a Float64 workspace of the context (packed: lda = m,
+// matrix k at k m n), the Float64 entry point with the caller's nb, rounded back.  `single`: the promoted tier calls
+// dhqr_factor_f64 / dhqr_solve_f64 (else the batched entry points).
+static int32_t f32_convert_launch(dhqr_ctx *c, bool widen, const void *src, int64_t lds, int64_t sstride, void *dst, int64_t ldd,
+                                  int64_t dstride, int64_t rows, int64_t cols, int64_t batch) {
+  const int64_t total = rows * cols * batch;
+  if (total <= 0) return DHQR_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
+  if (widen)
+    hipLaunchKernelGGL(k_widen_f32, dim3(grid), dim3(256), 0, c->stream, (const float *)src, lds, sstride, (double *)dst, ldd, dstride,
+                       rows, cols, batch);
+  else
+    hipLaunchKernelGGL(k_round_f32, dim3(grid), dim3(256), 0, c->stream, (const double *)src, lds, sstride, (float *)dst, ldd, dstride,
+                       rows, cols, batch);
+  LAUNCHCHECK();
+  return DHQR_OK;
+}
+
+static inline size_t f32_even(size_t n) { return (n + 1) & ~(size_t)1; }
+
+static int32_t f32_factor(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
+                          int64_t stride_alpha, int64_t batch, int32_t nb, bool single) {
+  if (batched_wave_fit(c, m, n)) {
+    // (tc_valid / retry stay: what they remember are Float64 buffers, which a Float32 factorisation cannot overwrite -- the
+    // promoted tier's workspace goes through dhqr_factor_f64, which resets them itself)
+    CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
+    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+    if (n <= 8)
+      hipLaunchKernelGGL((k_batched_qr_wave_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    else if (n <= 16)
+      hipLaunchKernelGGL((k_batched_qr_wave_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    else
+      hipLaunchKernelGGL((k_batched_qr_wave_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+    LAUNCHCHECK();
+    if (c->profiling)
+      for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 8.0 * (double)(m - j) * (double)(n - j - 1);
+    return prof_end(c);
+  }
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->f32_ws, f32_even(na) + nal));
+  double *wA = c->f32_ws.p, *wal = wA + f32_even(na);  // (sections on 16-byte boundaries, like separately allocated arrays)
+  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
+  // synchronous where the Float64 route is: the blocked driver of a single matrix, the serial tier of a batch
+  const bool sync = small_qr_fit(c, m, n) < 0 && (!single || nb != 0);
+  CHECK(single ? dhqr_factor_f64(c, wA, m, n, m, wal, nb) : dhqr_factor_batched_f64(c, wA, m, n, m, m * n, wal, n, batch, nb));
+  CHECK(f32_convert_launch(c, false, wA, m, m * n, dA, lda, strideA, m, n, batch));
+  CHECK(f32_convert_launch(c, false, wal, n, n, dalpha, n, stride_alpha, n, 1, batch));
+  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
+  return DHQR_OK;
+}
+
+static int32_t f32_solve(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
+                         int64_t stride_alpha, float *db, int64_t strideb, int64_t batch, bool single) {
+  if (batched_wave_fit(c, m, n)) {
+    CHECK(prof_begin(c, CAT_SOLVE));
+    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+    if (n <= 8)
+      hipLaunchKernelGGL((k_batched_ldiv_wave_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    else if (n <= 16)
+      hipLaunchKernelGGL((k_batched_ldiv_wave_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    else
+      hipLaunchKernelGGL((k_batched_ldiv_wave_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+    LAUNCHCHECK();
+    return prof_end(c);
+  }
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->f32_ws, f32_even(na) + f32_even(nal) + (size_t)m * (size_t)batch));
+  double *wA = c->f32_ws.p, *wal = wA + f32_even(na), *wb = wal + f32_even(nal);
+  if (c->tc_A == wA) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
+  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
+  CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, wal, n, n, n, 1, batch));
+  CHECK(f32_convert_launch(c, true, db, m, strideb, wb, m, m, m, 1, batch));
+  const bool sync = !single && !small_ldiv_fit(c, m, n);  // (the serial tier of a batch)
+  CHECK(single ? dhqr_solve_f64(c, wA, m, n, m, wal, wb) : dhqr_solve_batched_f64(c, wA, m, n, m, m * n, wal, n, wb, m, batch));
+  if (single && c->retry.valid && c->retry.b == wb) {  // (a flag left by an earlier Float64 solve names another b)
+    // THIS solve took the persistent Q'b kernel and may be REPEATED by the next synchronising entry point (dhqr.h:
+    // dhqr_get_solve_retries) -- into the workspace, behind the rounding enqueued below.  Settle it first; afterwards nothing
+    // may come back to the remembered pointers: they lie in a workspace that a later call may reallocate.
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    const int32_t rc = pipe_error_check(c);
+    c->retry.valid = false;
+    CHECK(rc);
+  }
+  CHECK(f32_convert_launch(c, false, wb, m, m, db, m, strideb, m, 1, batch));
+  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
+  return DHQR_OK;
+}
+
+// packed device staging of the host forms, in floats: matrices | alphas | right-hand sides
+static int32_t f32_dev_ensure(dhqr_ctx *c, size_t nfloats) { return ensure(c, c->f32_dev, (nfloats + 1) / 2); }
+// host <-> device copies of `batch` blocks of rows x cols floats (batch_copy for Float32)
+static int32_t batch_copy_f32(dhqr_ctx *c, float *d, const float *h, int64_t rows, int64_t cols, int64_t hld, int64_t hstride,
+                              int64_t batch, bool up) {
+  auto copy2d = [&](float *dp, const float *hp, int64_t dpitch, int64_t hpitch, int64_t width, int64_t height) -> int32_t {
+    if (up)
+      HIPCHECK(hipMemcpy2DAsync(dp, dpitch * sizeof(float), hp, hpitch * sizeof(float), width * sizeof(float), height,
+                                hipMemcpyHostToDevice, c->stream));
+    else
+      HIPCHECK(hipMemcpy2DAsync(const_cast<float *>(hp), hpitch * sizeof(float), dp, dpitch * sizeof(float), width * sizeof(float),
+                                height, hipMemcpyDeviceToHost, c->stream));
+    return DHQR_OK;
+  };
+  if (hld == rows || cols == 1) return copy2d(d, h, rows * cols, hstride, rows * cols, batch);  // every block contiguous
+  if (hstride == hld * cols) return copy2d(d, h, rows, hld, rows, cols * batch);               // one column pitch throughout
+  for (int64_t k = 0; k < batch; ++k) CHECK(copy2d(d + k * rows * cols, h + k * hstride, rows, hld, rows, cols));
+  return DHQR_OK;
+}
+
+static int32_t f32_qr_host(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
+                           int64_t stride_alpha, int64_t batch, int32_t nb, bool single) {
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(f32_dev_ensure(c, na + nal));
+  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na;
+  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
+  int32_t rc = f32_factor(c, dA, m, n, m, m * n, dal, n, batch, nb, single);
+  if (rc == DHQR_OK) rc = batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, false);
+  if (rc == DHQR_OK) rc = batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, false);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);
+  return rc;
+}
+
+static int32_t f32_ldiv_host(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *halpha,
+                             int64_t stride_alpha, const float *hb, int64_t strideb, float *hx, int64_t stridex, int64_t batch,
+                             bool single) {
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(f32_dev_ensure(c, na + nal + (size_t)m * (size_t)batch));
+  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na, *db = dal + nal;
+  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
+  CHECK(batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
+  CHECK(batch_copy_f32(c, db, hb, m, 1, m, strideb, batch, true));  // src:318 copy of b
+  int32_t rc = f32_solve(c, dA, m, n, m, m * n, dal, n, db, m, batch, single);
+  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);
+  if (rc == DHQR_OK)  // src:320: x_k = the first n entries of b_k
+    HIPCHECK(hipMemcpy2DAsync(hx, stridex * sizeof(float), db, m * sizeof(float), n * sizeof(float), batch, hipMemcpyDeviceToHost,
+                              c->stream));
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  return rc;
+}
+
+static int32_t check_nb(int32_t nb) {
+  if (nb != 0 && nb != DHQR_NB) return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
+  return DHQR_OK;
+}
+
+int32_t dhqr_factor_f32(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, float *dalpha, int32_t nb) {
+  ENTER(c);
+  if (no_columns(m, n)) return DHQR_OK;
+  CHECK(check_mat(dA, m, n, lda, true));
+  if (!dalpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  CHECK(check_nb(nb));
+  return f32_factor(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, 1, nb, true);
+}
+
+int32_t dhqr_qr_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, float *halpha, int32_t nb) {
+  ENTER(c);
+  if (no_columns(m, n)) return DHQR_OK;
+  CHECK(check_mat(hA, m, n, lda, true));
+  if (!halpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  CHECK(check_nb(nb));
+  return f32_qr_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, 1, nb, true);
+}
+
+int32_t dhqr_solve_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, const float *dalpha, float *db) {
+  ENTER(c);
+  if (no_columns(m, n)) return DHQR_OK;
+  CHECK(check_mat(dA, m, n, lda, true));
+  if (!dalpha || !db) return set_err(DHQR_EINVAL, "null alpha or b pointer");
+  return f32_solve(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, db, m, 1, true);
+}
+
+int32_t dhqr_ldiv_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, const float *halpha, const float *hb,
+                      float *hx) {
+  ENTER(c);
+  if (no_columns(m, n)) return DHQR_OK;
+  CHECK(check_mat(hA, m, n, lda, true));
+  if (!halpha || !hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
+  return f32_ldiv_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, hb, m, hx, n, 1, true);
+}
+
+int32_t dhqr_factor_batched_f32(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
+                                int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  CHECK(check_nb(nb));
+  return f32_factor(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nb, false);
+}
+
+int32_t dhqr_solve_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const float *dalpha, int64_t stride_alpha, float *db, int64_t strideb, int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  if (!db) return set_err(DHQR_EINVAL, "null b pointer");
+  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
+  return f32_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch, false);
+}
+
+int32_t dhqr_qr_batched_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
+                            int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  CHECK(check_nb(nb));
+  return f32_qr_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, batch, nb, false);
+}
+
+int32_t dhqr_ldiv_batched_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const float *halpha, int64_t stride_alpha, const float *hb, int64_t strideb, float *hx,
+                              int64_t stridex, int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  if (!hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
+  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
+  if (stridex < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)stridex, (long long)n);
+  return f32_ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hb, strideb, hx, stridex, batch, false);
 }
 
 int32_t dhqr_partialdot_f64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,

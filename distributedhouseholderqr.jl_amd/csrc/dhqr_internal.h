@@ -138,6 +138,8 @@ struct dhqr_ctx {
   Buf small_dev;                // device copy of a host factor inside k_small_ldiv (256 x 256)
   unsigned long long small_epoch = 0;  // launches that signalled their end through the pinned word behind small_pin
   Buf batch_dev;                // device copy of the batch (matrices | alphas | right-hand sides) of dhqr_qr_batched_f64 / dhqr_ldiv_batched_f64
+  Buf f32_ws;                   // Float64 workspace of the promoted Float32 tier (matrices | alphas | right-hand sides, dhqr_f32.h)
+  Buf f32_dev;                  // device staging of the Float32 host forms (floats, two per element of the Buf)
   int batched_wave = 1;         // batches of matrices of at most 64 x 32: one wave per matrix (dhqr_batched.h; DHQR_TUNE batched_wave=0: the one-CU kernels)
   bool coop = false;     // the device runs cooperative (all-resident) launches: false on the CPU emulator
   Buf host_mat;          // device copy of the caller's HOST matrix (+ alpha) of dhqr_qr_f64, kept between calls

@@ -112,6 +112,36 @@ function LinearAlgebra.:(\)(H::DistributedHouseholderQRStruct, b::AbstractVector
   return solve_householder!(s, H.A, H.α)
 end
 
+# ---- Float32 methods ---------------------------------------------------------------------------
+# The reference's qr! and `\` are generic over the element type (src:42-49, 306-321).  Up to 64 x 32 the library runs native
+# Float32 kernels (float storage, double sums); every other shape is widened on the device, runs the Float64 route chosen by
+# nb and is rounded back: float32(f64_route(float64(A))).  Float32 crosses PCIe.  `H \ b` is the generic method above.
+default_nb(A::StridedMatrix{Float32}) = size(A, 1) <= 480 ? 0 : DHQR_NB
+function householder!(A::StridedMatrix{Float32}, α::Vector{Float32}; nb::Integer=default_nb(A))
+  m, n = size(A)
+  stride(A, 1) == 1 || throw(ArgumentError("column-major storage required"))
+  check(ccall((:dhqr_qr_f32, libdhqr), Int32,
+              (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Int32),
+              context(), A, m, n, stride(A, 2), α, Int32(nb)))
+  return (A, α)
+end
+
+function qr!(A::StridedMatrix{Float32}; nb::Integer=default_nb(A))   # src:311-315
+  H = DistributedHouseholderQRStruct(A)
+  householder!(H.A, H.α; nb=nb)
+  return H
+end
+
+function solve_householder!(b::Vector{Float32}, H::StridedMatrix{Float32}, α::Vector{Float32})   # src:284-294
+  m, n = size(H)
+  x = Vector{Float32}(undef, n)
+  check(ccall((:dhqr_ldiv_f32, libdhqr), Int32,
+              (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+              context(), H, m, n, stride(H, 2), α, b, x))
+  b[1:n] .= x
+  return x
+end
+
 # ---- ComplexF64 methods ------------------------------------------------------------------------
 # nb = 64 (default for n >= 256): panels of 64 complex reflectors, trailing update on the FP64 MFMA kernels through the
 # real 2 x 2 embedding; nb = 0: the reference's unblocked order (src:171-196).  Same factorisation either way.

@@ -34,7 +34,9 @@ extern "C" {
 #endif
 
 #define DHQR_VERSION 500 /* 0.5.0: round 6 (dhqr_set_small_route added; nothing else changed); since then added, nothing changed:
-                          * dhqr_factor_batched_f64, dhqr_solve_batched_f64, dhqr_qr_batched_f64, dhqr_ldiv_batched_f64 */
+                          * dhqr_factor_batched_f64, dhqr_solve_batched_f64, dhqr_qr_batched_f64, dhqr_ldiv_batched_f64;
+                          * dhqr_factor_f32, dhqr_solve_f32, dhqr_qr_f32, dhqr_ldiv_f32, dhqr_factor_batched_f32, dhqr_solve_batched_f32,
+                          * dhqr_qr_batched_f32, dhqr_ldiv_batched_f32 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -230,6 +232,56 @@ int32_t dhqr_qr_batched_f64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int
                             double *halpha, int64_t stride_alpha, int64_t batch, int32_t nb);
 int32_t dhqr_ldiv_batched_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                               const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
+                              int64_t stridex, int64_t batch);
+
+/* ------------------------------------------------------------------ Float32 methods
+ * The reference's qr! and `\` are generic over the element type (partialdot(a, b, is, ::Type{<:Real}) src:42-49, qr!(A)
+ * src:306-315): `qr!(rand(Float32, m, n)) \ b` works there.  These are the Float32 counterparts of the four single-matrix and
+ * the four batched Float64 entry points above: the same arguments with `float *` in place of `double *`, the same
+ * conventions, error codes (DHQR_EINVAL conditions, the n == 0 and batch == 0 no-ops) and factor format, in Float32.  Device
+ * pointers need 4-byte alignment only.
+ * Routes by shape, in this order:
+ *   m <= 64 and n <= 32      NATIVE: one launch, one WAVE per matrix (csrc/dhqr_f32.h; a single matrix is a batch of 1).  The
+ *                            matrix is stored in float, every sum (column norm, v_j' a_c) is taken in double -- the product of
+ *                            two floats is exact there --, alpha / f / pivot are formed in double, every stored entry is
+ *                            rounded to float once per column step; the solve carries b in double and rounds each entry once.
+ *                            With profiling on a factor counts ONE n_rank1 group and a solve one n_solve, whatever the batch.
+ *   everything else, and every shape when the small route is off (dhqr_set_small_route(ctx, 0), DHQR_SMALL=0)
+ *                            PROMOTED: a kernel widens the matrix (for a solve: the factor, alpha and b) into a Float64
+ *                            workspace of the context (packed, lda = m), the Float64 entry point of the same name runs on it
+ *                            with the caller's nb (so its small route, one-CU batched tier, unblocked and blocked paths are all
+ *                            reachable), a second kernel rounds the result to the caller's arrays, to nearest-even:
+ *                                result = float32(f64_entry_point(float64(input)))   by definition.
+ *                            A value outside Float32's range rounds to +-inf.  The workspace stays in the context; dhqr_trim
+ *                            releases it; a failed allocation is DHQR_ENOMEM.
+ *                            A native Float32 path for large matrices (FP32 MFMA trailing updates) does not exist.
+ * Synchronisation follows the Float64 route taken:
+ *   dhqr_factor_f32          asynchronous on the native tier, on the Float64 small route and with nb == 0; synchronous with
+ *                            nb == DHQR_NB beyond the small route (the blocked driver).
+ *   dhqr_solve_f32           asynchronous on the native tier and on the Float64 small route; beyond it the call waits for the
+ *                            Float64 solve whenever that took the persistent Q'b kernel (a repetition, dhqr_get_solve_retries,
+ *                            must land before the result is rounded); the rounding itself is enqueued.  Like every asynchronous
+ *                            entry point: results are valid after dhqr_synchronize returned DHQR_OK.
+ *   dhqr_factor_batched_f32 / dhqr_solve_batched_f32
+ *                            asynchronous on the native tier and on the one-workgroup-per-matrix tier; synchronous on the
+ *                            serial tier.
+ *   dhqr_qr_f32, dhqr_ldiv_f32, dhqr_qr_batched_f32, dhqr_ldiv_batched_f32
+ *                            host in / host out, synchronous: Float32 crosses PCIe (half the bytes of the Float64 forms), the
+ *                            conversion happens on the device.  The device copy stays in the context (dhqr_trim).  On an error
+ *                            return hA is undefined; hb is not modified. */
+int32_t dhqr_factor_f32(dhqr_ctx *ctx, float *dA, int64_t m, int64_t n, int64_t lda, float *dalpha, int32_t nb);
+int32_t dhqr_solve_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, const float *dalpha, float *db);
+int32_t dhqr_qr_f32(dhqr_ctx *ctx, float *hA, int64_t m, int64_t n, int64_t lda, float *halpha, int32_t nb);
+int32_t dhqr_ldiv_f32(dhqr_ctx *ctx, const float *hA, int64_t m, int64_t n, int64_t lda, const float *halpha, const float *hb,
+                      float *hx);
+int32_t dhqr_factor_batched_f32(dhqr_ctx *ctx, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
+                                int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_solve_batched_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const float *dalpha, int64_t stride_alpha, float *db, int64_t strideb, int64_t batch);
+int32_t dhqr_qr_batched_f32(dhqr_ctx *ctx, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
+                            int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_ldiv_batched_f32(dhqr_ctx *ctx, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const float *halpha, int64_t stride_alpha, const float *hb, int64_t strideb, float *hx,
                               int64_t stridex, int64_t batch);
 
 /* KAT hook mirroring partialdot(a, b, lo:hi, Float64) (src:42-49; test/partialdot.jl:18):

@@ -3,6 +3,9 @@ a loop of `batch` single calls (dhqr_factor_f64 with the small route on, then dh
 
 usage: python tools/batched_bench.py [--out FILE]          every point, each in a child process under `timeout -k 10`
        python tools/batched_bench.py --point M N BATCH     one point (what the children run)
+       --dtype f32                                         the Float32 entry points (dhqr_*_f32: native kernels up to 64 x 32,
+                                                           the promoted tier beyond), same points, same columns
+       --shapes 16x8,32x16                                 only these shapes (default: every shape of SHAPES)
 
 Per point: 3 warm-up and 10 timed repetitions of (restore the inputs, synchronise, START, calls, synchronise, STOP) on the
 host clock -- a caller's view, launch costs included; median and min-max of matrices per second; the ratio batched / looped
@@ -23,20 +26,22 @@ BATCHES = [64, 1024, 16384]
 WARMUP, REPS = 3, 10
 
 
-def point(m, n, batch):
+def point(m, n, batch, dtype="f64"):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as g
     pkg = g.import_package()
     batch = min(batch, (4 << 30) // (m * n * 8) - 1)  # the batch stays under 4 GiB
-    A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0")
-    b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
+    b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0", dtype=tdt).reshape(batch, m).contiguous()
     A, b = A0.clone(), b0.clone()
-    al = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    al = torch.zeros((batch, n), dtype=tdt, device="cuda:0")
     torch.cuda.synchronize()
     L = pkg._lib.lib()
     P = ctypes.c_void_p
     pa, pal, pb = A.data_ptr(), al.data_ptr(), b.data_ptr()
+    factor_b, solve_b, factor_1, solve_1 = (getattr(L, f"dhqr_{k}_{dtype}") for k in ("factor_batched", "solve_batched", "factor", "solve"))
     os.environ["DHQR_SMALL"] = "1"
 
     def measure(ctx, fn):
@@ -54,22 +59,24 @@ def point(m, n, batch):
         return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
 
     def batched(h):
-        pkg._lib.check(L.dhqr_factor_batched_f64(h, P(pa), m, n, m, m * n, P(pal), n, batch, 0))
-        pkg._lib.check(L.dhqr_solve_batched_f64(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), m, batch))
+        pkg._lib.check(factor_b(h, P(pa), m, n, m, m * n, P(pal), n, batch, 0))
+        pkg._lib.check(solve_b(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), m, batch))
 
     def looped(h):
         for k in range(batch):
-            ak, alk = P(pa + 8 * k * m * n), P(pal + 8 * k * n)
-            pkg._lib.check(L.dhqr_factor_f64(h, ak, m, n, m, alk, 0))
-            pkg._lib.check(L.dhqr_solve_f64(h, ak, m, n, m, alk, P(pb + 8 * k * m)))
+            ak, alk = P(pa + esz * k * m * n), P(pal + esz * k * n)
+            pkg._lib.check(factor_1(h, ak, m, n, m, alk, 0))
+            pkg._lib.check(solve_1(h, ak, m, n, m, alk, P(pb + esz * k * m)))
 
-    out = {"m": m, "n": n, "batch": batch}
+    out = {"m": m, "n": n, "batch": batch, "dtype": dtype}
     ctx = pkg.Context(0)
     out["batched"] = measure(ctx, batched)
     x = b[:, :n].clone()
     out["looped"] = measure(ctx, looped)
     ctx.close()
     if m <= 64 and n <= 32:
+        if dtype == "f32":
+            assert torch.equal(x, b[:, :n]), "a single Float32 matrix is a batch of 1: the same bits"
         assert ((x - b[:, :n]).abs().amax(dim=1) <= 1e-9 * x.abs().amax(dim=1)).all(), "batched and looped solutions differ"
         os.environ["DHQR_TUNE"] = "batched_wave=0"
         ctx = pkg.Context(0)
@@ -88,19 +95,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--point", nargs=3, type=int)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=("f64", "f32"), default="f64")
+    ap.add_argument("--shapes", default=None, help="e.g. 16x8,32x16 (default: every shape)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
     a = ap.parse_args()
     if a.point:
-        point(*a.point)
+        point(*a.point, a.dtype)
         return 0
+    t = a.dtype
+    shapes = SHAPES if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
     lines = ["# tools/batched_bench.py: qr! + \\ of `batch` matrices, matrices per second, median (min .. max) of 10 repetitions",
-             "# batched = one dhqr_factor_batched_f64 + one dhqr_solve_batched_f64; looped = batch x (dhqr_factor_f64 + dhqr_solve_f64), small route on",
+             f"# batched = one dhqr_factor_batched_{t} + one dhqr_solve_batched_{t}; looped = batch x (dhqr_factor_{t} + dhqr_solve_{t}), small route on",
              "# one-CU = the batched calls with DHQR_TUNE batched_wave=0 (one workgroup per matrix) on the wave tier's shapes"]
     print("\n".join(lines), flush=True)
-    for (m, n) in SHAPES:
+    for (m, n) in shapes:
         for batch in BATCHES:
             p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
-                                str(m), str(n), str(batch)], capture_output=True, text=True)
+                                str(m), str(n), str(batch), "--dtype", t], capture_output=True, text=True)
             row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
             if p.returncode != 0 or not row:
                 lines.append(f"{m}x{n} batch {batch}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
