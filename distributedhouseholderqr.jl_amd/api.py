@@ -3,7 +3,7 @@
 Reference (src/DistributedHouseholderQR.jl)        here
   qr!(A)                         :311-315          qr_(A, nb=...)             ('!' -> trailing '_')
   DistributedHouseholderQRStruct :296-309          DistributedHouseholderQRStruct(A, α)
-  H \\ b                          :317-321          ldiv(H, b)  /  H.solve(b)
+  H \\ b                          :317-321          ldiv(H, b)  /  H.solve(b)   (b a vector, or a matrix of right-hand sides)
   householder!(A, α)             :113-120          householder_(A, α, nb=...)
   solve_householder!(b, H, α)    :284-294          solve_householder_(b, H, α)
   partialdot(a, b, is, T)        :42-49, :51-59    partialdot(a, b, lo, hi)
@@ -363,11 +363,61 @@ def qr_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
     return H
 
 
+def _solve_nrhs(B, H, α):
+    """solve_householder!(B, H, α) for a MATRIX B (m, nrhs) of right-hand sides and one real factor (a batch of 1 of
+    dhqr_solve_batched_nrhs_* / dhqr_ldiv_batched_nrhs_*): returns X (n, nrhs), column-major.  A device B (column-major) is
+    overwritten with [X; tail of Q'B]; a host B in any layout is left untouched."""
+    L = _lib.lib()
+    f32 = _is_f32(H)
+    if _is_tensor(H):
+        dt = torch.float32 if f32 else torch.float64
+        ptr, m, n, lda, dev = _dev_matrix(H, dt)
+        if not _is_tensor(B):
+            raise TypeError(f"column-major {dt} CUDA tensor of shape ({m}, nrhs) expected")
+        bptr, mb, nrhs, ldb, _ = _dev_matrix(B, dt)
+        if mb != m:
+            raise ValueError(f"B has {mb} rows, the factor {m}")
+        solve = L.dhqr_solve_batched_nrhs_f32 if f32 else L.dhqr_solve_batched_nrhs_f64
+        ctx = get_context(dev)
+        ctx.use_torch_stream()
+        check(solve(ctx.handle, ptr, m, n, lda, max(lda * (n - 1) + m, 1), _dev_vector(α, n, dt), max(n, 1),
+                    bptr, nrhs, ldb, max(ldb * (nrhs - 1) + m, 1), 1))
+        ctx.synchronize()
+        X = empty_colmajor(n, nrhs, B.device, dt)
+        X.copy_(B[:n])
+        return X
+    dt = np.float32 if f32 else np.float64
+    m, n = H.shape
+    F = H if H.flags.f_contiguous else np.asfortranarray(H)
+    Bf = np.asfortranarray(B, dtype=dt)  # (a copy only where the layout asks for one; never written)
+    if Bf.ndim != 2 or Bf.shape[0] != m:
+        raise ValueError(f"B must have shape ({m}, nrhs)")
+    nrhs = Bf.shape[1]
+    X = np.empty((n, nrhs), dtype=dt, order="F")
+    ldiv_ = L.dhqr_ldiv_batched_nrhs_f32 if f32 else L.dhqr_ldiv_batched_nrhs_f64
+    check(ldiv_(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, _host_ld(F), max(_host_ld(F) * (n - 1) + m, 1),
+                np.ascontiguousarray(α, dtype=dt).ctypes.data_as(ctypes.c_void_p), max(n, 1),
+                Bf.ctypes.data_as(ctypes.c_void_p), nrhs, max(m, 1), max(m * nrhs, 1),
+                X.ctypes.data_as(ctypes.c_void_p), max(n, 1), max(n * nrhs, 1), 1))
+    return X
+
+
 def solve_householder_(b, H, α):
     """solve_householder!(b, H, α) (src:284-294): returns x = b[1:n] (a copy, like Julia's b[1:n]).  A device
     tensor b is overwritten like the reference's b (b <- Q'b, then back substitution in place); a HOST b is
-    uploaded and left untouched (the solve happens in device memory)."""
+    uploaded and left untouched (the solve happens in device memory).  A matrix b (m, nrhs) -- column-major on the
+    device, any layout on the host -- solves all its columns in one call and returns X (n, nrhs), column-major;
+    Float64 and Float32.  Column r of X has the bits of ldiv_batched on a batch of one with the vector b[:, r].  For a
+    Float64 factor of at most 64 x 32 that is NOT the route a vector b takes here (dhqr_solve_f64: the one-workgroup
+    kernel, against the wave kernel of the batched entry points), so X[:, r] and solve_householder_(b[:, r], H, α) may
+    differ in the last bits there; beyond those shapes, and in Float32, they are identical."""
     L = _lib.lib()
+    if getattr(b, "ndim", 1) == 2 and H.ndim == 2:
+        if _is_complex(H):
+            raise TypeError("ComplexF64: vector right-hand side only")
+        _same_dtype(H, α, "α")
+        _same_dtype(H, b, "b")
+        return _solve_nrhs(b, H, α)
     if _is_complex(H):
         if _is_tensor(H):
             ptr, m, n, lda, dev = _dev_matrix(H, torch.complex128)
@@ -425,9 +475,18 @@ def solve_householder_(b, H, α):
 
 def ldiv(H: DistributedHouseholderQRStruct, b):
     """`H \\ b` (src:317-321): least-squares solution of length n; the caller's b is NOT modified
-    (the reference copies it into a SharedArray first, src:318)."""
+    (the reference copies it into a SharedArray first, src:318).  `H \\ B` with a matrix B of as many dimensions as H.A
+    -- (m, nrhs), or (batch, m, nrhs) for a batch -- solves every column: X (n, nrhs) / (batch, n, nrhs), column-major.
+    X[..., r] has the bits of ldiv_batched on the vectors B[..., r] (a single matrix: a batch of one).  ldiv(H, B[:, r]) of one
+    Float64 factor of at most 64 x 32 runs another kernel and may differ from X[:, r] in the last bits (solve_householder_)."""
     if H.A.ndim == 3:
         return ldiv_batched(H, b)
+    if _is_tensor(H.A) and _is_tensor(b) and b.dim() == 2 and not _is_complex(H.A):
+        _same_dtype(H.A, b, "b")
+        _dev_matrix(b, H.A.dtype)  # (the dtype and layout rules, before the copy hides them)
+        W = empty_colmajor(b.shape[0], b.shape[1], b.device, H.A.dtype)
+        W.copy_(b)  # src:318 copy of B
+        return solve_householder_(W, H.A, H.α)
     if _is_tensor(H.A):
         return solve_householder_(b.clone(), H.A, H.α)
     return solve_householder_(b, H.A, H.α)
@@ -523,8 +582,67 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
     return H
 
 
+def _host_batch(A):
+    """(array, lda, strideA) of a (batch, rows, cols) host array with column-major matrices: A itself where its layout
+    allows, else a copy in that layout"""
+    batch, rows, cols = A.shape
+    lay = None
+    if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
+        lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
+    if lay is not None:
+        return A, lay[0], lay[1]
+    F = np.empty((batch, cols, rows), dtype=A.dtype).transpose(0, 2, 1)
+    F[...] = A
+    return F, max(rows, 1), max(rows * cols, 1)
+
+
+def _ldiv_batched_nrhs(H: DistributedHouseholderQRStruct, B):
+    """ldiv_batched for B (batch, m, nrhs): dhqr_solve_batched_nrhs_* on a copy of a device B, dhqr_ldiv_batched_nrhs_*
+    on a host B; X (batch, n, nrhs) with column-major matrices"""
+    L = _lib.lib()
+    A, α = H.A, H.α
+    batch, m, n = A.shape
+    f32 = _is_f32(A)
+    solve, ldiv_ = ((L.dhqr_solve_batched_nrhs_f32, L.dhqr_ldiv_batched_nrhs_f32) if f32
+                    else (L.dhqr_solve_batched_nrhs_f64, L.dhqr_ldiv_batched_nrhs_f64))
+    if _is_tensor(A):
+        lay = _batch_layout(A.shape, A.stride())
+        if lay is None:
+            raise ValueError("matrices of the batch must be column-major (stride(1) == 1)")
+        if not _is_tensor(B) or B.dtype != A.dtype or not B.is_cuda or tuple(B.shape[:2]) != (batch, m):
+            raise TypeError(f"{A.dtype} CUDA tensor of shape ({batch}, {m}, nrhs) expected")
+        if _batch_layout(B.shape, B.stride()) is None:
+            raise ValueError("matrices of B must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
+        if α.dtype != A.dtype or tuple(α.shape) != (batch, n) or not α.is_contiguous():
+            raise TypeError(f"α must be a contiguous {A.dtype} tensor of shape ({batch}, {n})")
+        nrhs = B.shape[2]
+        W = empty_colmajor_batched(batch, m, nrhs, B.device, A.dtype)
+        W.copy_(B)  # src:318 copy of B
+        ctx = get_context(A.device.index)
+        ctx.use_torch_stream()
+        check(solve(ctx.handle, ctypes.c_void_p(A.data_ptr()), m, n, lay[0], lay[1], ctypes.c_void_p(α.data_ptr()), max(n, 1),
+                    ctypes.c_void_p(W.data_ptr()), nrhs, max(m, 1), max(m * nrhs, 1), batch))
+        ctx.synchronize()
+        X = empty_colmajor_batched(batch, n, nrhs, B.device, A.dtype)
+        X.copy_(W[:, :n, :])
+        return X
+    B = np.asarray(B, dtype=A.dtype)
+    if B.shape[:2] != (batch, m):
+        raise ValueError(f"B must have shape ({batch}, {m}, nrhs)")
+    nrhs = B.shape[2]
+    F, lda, strideA = _host_batch(A)
+    Bf, ldb, strideB = _host_batch(B)
+    al, sal = _host_rows(α, batch, n, "α", A.dtype)
+    X = np.empty((batch, nrhs, n), dtype=A.dtype).transpose(0, 2, 1)
+    check(ldiv_(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lda, strideA,
+                al.ctypes.data_as(ctypes.c_void_p), sal, Bf.ctypes.data_as(ctypes.c_void_p), nrhs, ldb, strideB,
+                X.ctypes.data_as(ctypes.c_void_p), max(n, 1), max(n * nrhs, 1), batch))
+    return X
+
+
 def ldiv_batched(H: DistributedHouseholderQRStruct, b):
-    """`H[k] \\ b[k]` for every matrix of a batched factorisation: b (batch, m) -> x (batch, n); b is NOT modified."""
+    """`H[k] \\ b[k]` for every matrix of a batched factorisation: b (batch, m) -> x (batch, n); b is NOT modified.
+    b (batch, m, nrhs), its matrices column-major like A's: every column of every b[k] -> X (batch, n, nrhs)."""
     L = _lib.lib()
     A, α = H.A, H.α
     if A.ndim != 3:
@@ -533,6 +651,8 @@ def ldiv_batched(H: DistributedHouseholderQRStruct, b):
     f32 = _is_f32(A)
     _same_dtype(A, α, "α")
     _same_dtype(A, b, "b")
+    if getattr(b, "ndim", 2) == 3:
+        return _ldiv_batched_nrhs(H, b)
     solve, ldiv_ = (L.dhqr_solve_batched_f32, L.dhqr_ldiv_batched_f32) if f32 else (L.dhqr_solve_batched_f64, L.dhqr_ldiv_batched_f64)
     if _is_tensor(A):
         lay = _batch_layout(A.shape, A.stride())

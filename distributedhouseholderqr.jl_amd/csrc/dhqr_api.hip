@@ -15,6 +15,7 @@
 #include "dhqr_small.h"
 #include "dhqr_batched.h"
 #include "dhqr_f32.h"
+#include "dhqr_batched_nrhs.h"
 #include "dhqr_tsqr.h"
 
 static thread_local char g_err[512] = "";
@@ -2378,6 +2379,173 @@ int32_t dhqr_ldiv_batched_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n
   if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
   if (stridex < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)stridex, (long long)n);
   return f32_ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hb, strideb, hx, stridex, batch, false);
+}
+
+// ---- several right-hand sides per matrix (dhqr.h: dhqr_solve_batched_nrhs_f64 ...) ------------------------------------
+// The wave tier: ONE launch of the multi-column kernels of dhqr_batched_nrhs.h.  Every other shape: the existing
+// single-column entry point, column by column -- its tiers, its synchronisation, its profiling counts, its bits.
+// Does the multi-column kernel pay?  Measured (profiles/batched_nrhs_throughput.txt, batch 16384): the kernel is bound by
+// instruction issue, not by re-reading the matrix, and its time goes by GROUPS -- a group of rg chains costs 2.5 to 3.0
+// single-column solves whether its columns are real or the zeros of a tail.  nrhs = 2 loses everywhere (0.62 - 0.81 x the
+// column loop), nrhs = 4 in groups of three (Float64, n > 8) loses (0.77 - 0.80 x); nrhs = 4 in groups of four, 8 and 16 win
+// (1.01 - 1.23 x).  So: the kernel where the groups carry at least 2.6 real columns on average, the column loop -- the
+// same bits -- elsewhere.
+static inline bool nrhs_wave_pays(int64_t nrhs, int rg) {
+  const int64_t groups = (nrhs + rg - 1) / rg;
+  return 5 * nrhs >= 13 * groups;
+}
+static int32_t check_nrhs_sizes(int64_t nrhs, int64_t batch) {
+  if (nrhs < 0) return set_err(DHQR_EINVAL, "negative nrhs %lld", (long long)nrhs);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  return DHQR_OK;
+}
+static int32_t check_nrhs(const void *B, const char *name, int64_t rows, int64_t nrhs, int64_t ldb, int64_t strideB) {
+  if (!B) return set_err(DHQR_EINVAL, "null %s pointer", name);
+  if (nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "nrhs %lld too large", (long long)nrhs);
+  if (ldb < rows) return set_err(DHQR_EINVAL, "leading dimension of %s %lld < %lld", name, (long long)ldb, (long long)rows);
+  if (strideB < ldb * (nrhs - 1) + rows)
+    return set_err(DHQR_EINVAL, "stride of %s %lld < ld*(nrhs-1)+rows = %lld", name, (long long)strideB,
+                   (long long)(ldb * (nrhs - 1) + rows));
+  return DHQR_OK;
+}
+
+int32_t dhqr_solve_batched_nrhs_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch) {
+  ENTER(c);
+  CHECK(check_nrhs_sizes(nrhs, batch));
+  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  CHECK(check_nrhs(dB, "B", m, nrhs, ldb, strideB));
+  if (!batched_wave_fit(c, m, n) || !nrhs_wave_pays(nrhs, n <= 8 ? BQN_RG_D(8) : BQN_RG_D(32))) {
+    for (int64_t r = 0; r < nrhs; ++r)
+      CHECK(dhqr_solve_batched_f64(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
+    return DHQR_OK;
+  }
+  CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
+  const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+  if (n <= 8)
+    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  else if (n <= 16)
+    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  else
+    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  LAUNCHCHECK();
+  return prof_end(c);
+}
+
+int32_t dhqr_ldiv_batched_nrhs_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const double *halpha, int64_t stride_alpha, const double *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, double *hX, int64_t ldx, int64_t strideX, int64_t batch) {
+  ENTER(c);
+  CHECK(check_nrhs_sizes(nrhs, batch));
+  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  CHECK(check_nrhs(hB, "B", m, nrhs, ldb, strideB));
+  CHECK(check_nrhs(hX, "X", n, nrhs, ldx, strideX));
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->batch_dev, na + nal + (size_t)m * (size_t)nrhs * (size_t)batch));
+  double *dA = c->batch_dev.p, *dal = dA + na, *dB = dal + nal;
+  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
+  CHECK(batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
+  CHECK(batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true));  // src:318 copy of B
+  int32_t rc = dhqr_solve_batched_nrhs_f64(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch);
+  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);  // (the serial tier's solves may have been repeated: dhqr.h)
+  if (rc == DHQR_OK) {  // src:320: X_k = the first n rows of B_k
+    if (strideX == ldx * nrhs || batch == 1) {  // one column pitch throughout
+      if (hipMemcpy2DAsync(hX, ldx * sizeof(double), dB, m * sizeof(double), n * sizeof(double), nrhs * batch, hipMemcpyDeviceToHost,
+                           c->stream) != hipSuccess)
+        rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
+    } else {
+      for (int64_t k = 0; k < batch && rc == DHQR_OK; ++k)  // (a failed enqueue still reaches the synchronisation below)
+        if (hipMemcpy2DAsync(hX + k * strideX, ldx * sizeof(double), dB + k * m * nrhs, m * sizeof(double), n * sizeof(double),
+                             nrhs, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+          rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
+    }
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  return rc;
+}
+
+// Float32: the native multi-column kernel on the wave tier; everything else PROMOTED once -- factor, alpha and all of B
+// widened into the Float64 workspace, the Float64 entry point above, B rounded back.
+static int32_t f32_solve_nrhs(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
+                              int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
+  if (batched_wave_fit(c, m, n) && !nrhs_wave_pays(nrhs, BQN_RG)) {  // the native single-column kernel, column by column
+    for (int64_t r = 0; r < nrhs; ++r)
+      CHECK(f32_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch, false));
+    return DHQR_OK;
+  }
+  if (batched_wave_fit(c, m, n)) {
+    CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
+    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
+    if (n <= 8)
+      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+    else if (n <= 16)
+      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+    else
+      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+    LAUNCHCHECK();
+    return prof_end(c);
+  }
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(ensure(c, c->f32_ws, f32_even(na) + f32_even(nal) + (size_t)m * (size_t)nrhs * (size_t)batch));
+  double *wA = c->f32_ws.p, *wal = wA + f32_even(na), *wB = wal + f32_even(nal);
+  if (c->tc_A == wA) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
+  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
+  CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, wal, n, n, n, 1, batch));
+  CHECK(f32_convert_launch(c, true, dB, ldb, strideB, wB, m, m * nrhs, m, nrhs, batch));
+  const bool sync = !small_ldiv_fit(c, m, n);  // (the serial tier)
+  CHECK(dhqr_solve_batched_nrhs_f64(c, wA, m, n, m, m * n, wal, n, wB, nrhs, m, m * nrhs, batch));
+  CHECK(f32_convert_launch(c, false, wB, m, m * nrhs, dB, ldb, strideB, m, nrhs, batch));
+  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
+  return DHQR_OK;
+}
+
+int32_t dhqr_solve_batched_nrhs_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const float *dalpha, int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch) {
+  ENTER(c);
+  CHECK(check_nrhs_sizes(nrhs, batch));
+  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
+  CHECK(check_nrhs(dB, "B", m, nrhs, ldb, strideB));
+  return f32_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+}
+
+int32_t dhqr_ldiv_batched_nrhs_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const float *halpha, int64_t stride_alpha, const float *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, float *hX, int64_t ldx, int64_t strideX, int64_t batch) {
+  ENTER(c);
+  CHECK(check_nrhs_sizes(nrhs, batch));
+  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
+  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
+  CHECK(check_nrhs(hB, "B", m, nrhs, ldb, strideB));
+  CHECK(check_nrhs(hX, "X", n, nrhs, ldx, strideX));
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  CHECK(f32_dev_ensure(c, na + nal + (size_t)m * (size_t)nrhs * (size_t)batch));
+  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na, *dB = dal + nal;
+  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
+  CHECK(batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
+  CHECK(batch_copy_f32(c, dB, hB, m, nrhs, ldb, strideB, batch, true));  // src:318 copy of B
+  int32_t rc = f32_solve_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch);
+  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (rc == DHQR_OK) rc = pipe_error_check(c);
+  if (rc == DHQR_OK) {  // src:320: X_k = the first n rows of B_k
+    if (strideX == ldx * nrhs || batch == 1) {  // one column pitch throughout
+      if (hipMemcpy2DAsync(hX, ldx * sizeof(float), dB, m * sizeof(float), n * sizeof(float), nrhs * batch, hipMemcpyDeviceToHost,
+                           c->stream) != hipSuccess)
+        rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
+    } else {
+      for (int64_t k = 0; k < batch && rc == DHQR_OK; ++k)  // (a failed enqueue still reaches the synchronisation below)
+        if (hipMemcpy2DAsync(hX + k * strideX, ldx * sizeof(float), dB + k * m * nrhs, m * sizeof(float), n * sizeof(float), nrhs,
+                             hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+          rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
+    }
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  return rc;
 }
 
 int32_t dhqr_partialdot_f64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,

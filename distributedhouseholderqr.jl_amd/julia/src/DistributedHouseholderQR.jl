@@ -19,6 +19,7 @@
 #   reference                                 this module
 #   qr!(A)                      src:311-315   qr!(A; nb=default_nb(A))      -> dhqr_qr_f64
 #   H \ b                       src:317-321   \(H, b)                       -> dhqr_ldiv_f64
+#   H \ B (B a Matrix)          (new)         \(H, B)                       -> dhqr_ldiv_batched_nrhs_f64 / _f32
 #   householder!(A, α)          src:113       householder!(A, α; nb=...)    -> dhqr_qr_f64
 #   solve_householder!(b, H, α) src:284-294   solve_householder!(b, H, α)   -> dhqr_ldiv_f64
 #   partialdot(a, b, is, T)     src:42-49     partialdot(a, b, is, Float64) -> dhqr_partialdot_host_f64 (KAT hook)
@@ -140,6 +141,38 @@ function solve_householder!(b::Vector{Float32}, H::StridedMatrix{Float32}, α::V
               context(), H, m, n, stride(H, 2), α, b, x))
   b[1:n] .= x
   return x
+end
+
+# ---- H \ B for a matrix of right-hand sides ----------------------------------------------------
+# Every column of B against the same factor in ONE call (a batch of 1 of dhqr_ldiv_batched_nrhs_*): up to 64 x 32 the
+# factor is read once and the columns walk past it; beyond, the library runs one existing solve per column.  B is not
+# modified; X is n x nrhs.  Column r of X has the bits of the BATCHED single-column entry point (batch = 1) on B[:, r]; for a
+# Float64 factor of at most 64 x 32 that is the wave kernel, and H \ B[:, r] (dhqr_ldiv_f64: the one-workgroup kernel) may
+# differ from it in the last bits.
+function LinearAlgebra.:(\)(H::DistributedHouseholderQRStruct{<:StridedMatrix{Float64}}, B::Matrix{Float64})
+  m, n = size(H.A)
+  size(B, 1) == m || throw(DimensionMismatch("B has $(size(B, 1)) rows, the factor $m"))
+  nrhs = size(B, 2)
+  X = Matrix{Float64}(undef, n, nrhs)
+  check(ccall((:dhqr_ldiv_batched_nrhs_f64, libdhqr), Int32,
+              (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64,
+               Ptr{Float64}, Int64, Int64, Int64),
+              context(), H.A, m, n, stride(H.A, 2), max(stride(H.A, 2) * (n - 1) + m, 1), H.α, max(n, 1),
+              B, nrhs, max(m, 1), max(m * nrhs, 1), X, max(n, 1), max(n * nrhs, 1), 1))
+  return X
+end
+
+function LinearAlgebra.:(\)(H::DistributedHouseholderQRStruct{<:StridedMatrix{Float32}}, B::Matrix{Float32})
+  m, n = size(H.A)
+  size(B, 1) == m || throw(DimensionMismatch("B has $(size(B, 1)) rows, the factor $m"))
+  nrhs = size(B, 2)
+  X = Matrix{Float32}(undef, n, nrhs)
+  check(ccall((:dhqr_ldiv_batched_nrhs_f32, libdhqr), Int32,
+              (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Int64, Int64,
+               Ptr{Float32}, Int64, Int64, Int64),
+              context(), H.A, m, n, stride(H.A, 2), max(stride(H.A, 2) * (n - 1) + m, 1), H.α, max(n, 1),
+              B, nrhs, max(m, 1), max(m * nrhs, 1), X, max(n, 1), max(n * nrhs, 1), 1))
+  return X
 end
 
 # ---- ComplexF64 methods ------------------------------------------------------------------------

@@ -36,7 +36,9 @@ extern "C" {
 #define DHQR_VERSION 500 /* 0.5.0: round 6 (dhqr_set_small_route added; nothing else changed); since then added, nothing changed:
                           * dhqr_factor_batched_f64, dhqr_solve_batched_f64, dhqr_qr_batched_f64, dhqr_ldiv_batched_f64;
                           * dhqr_factor_f32, dhqr_solve_f32, dhqr_qr_f32, dhqr_ldiv_f32, dhqr_factor_batched_f32, dhqr_solve_batched_f32,
-                          * dhqr_qr_batched_f32, dhqr_ldiv_batched_f32 */
+                          * dhqr_qr_batched_f32, dhqr_ldiv_batched_f32;
+                          * dhqr_solve_batched_nrhs_f64, dhqr_ldiv_batched_nrhs_f64, dhqr_solve_batched_nrhs_f32,
+                          * dhqr_ldiv_batched_nrhs_f32 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -283,6 +285,56 @@ int32_t dhqr_qr_batched_f32(dhqr_ctx *ctx, float *hA, int64_t m, int64_t n, int6
 int32_t dhqr_ldiv_batched_f32(dhqr_ctx *ctx, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                               const float *halpha, int64_t stride_alpha, const float *hb, int64_t strideb, float *hx,
                               int64_t stridex, int64_t batch);
+
+/* ------------------------------------------------------------------ several right-hand sides per matrix
+ * `H_k \ B_k` for k = 0 .. batch-1 with a MATRIX B_k of nrhs right-hand sides (several channels fitted against the same
+ * small design matrix): what torch.linalg.lstsq or LAPACK's ormqr + trtrs do with a matrix B.  A single matrix is
+ * batch = 1.  Strided like the batched family above: B_k (m x nrhs, column-major, leading dimension ldb) starts at
+ * B + k*strideB, X_k (n x nrhs, leading dimension ldx) at X + k*strideX; column r of B_k is B + k*strideB + r*ldb.  The
+ * factor and alpha arguments are those of dhqr_solve_batched_f64 / _f32.
+ *   dhqr_solve_batched_nrhs_f64 / _f32  device-resident: dB_k (m x nrhs) <- [X_k; tail of Q'B_k], in place; asynchronous
+ *                                       wherever the single-column entry point of the same type is.
+ *   dhqr_ldiv_batched_nrhs_f64 / _f32   host in / host out; hB is not modified (src:318), hX_k (n x nrhs) is written;
+ *                                       synchronous; staged through the buffers of dhqr_ldiv_batched_f64 / _f32 (dhqr_trim).
+ * Column r of the result is BIT-IDENTICAL to what dhqr_solve_batched_f64 / _f32 returns for b_k = B_k[:, r] alone, on every
+ * route: it depends neither on nrhs nor on the column's position nor on the batch.
+ * That is the BATCHED single-column entry point, also for batch = 1.  dhqr_solve_f64 (one matrix, one vector) is another
+ * route for m <= 64 and n <= 32 -- the single-workgroup kernel of dhqr_set_small_route instead of the wave kernel --, and
+ * its result may differ from these in the last bits, exactly as it differs from dhqr_solve_batched_f64 with batch = 1.
+ * Beyond those shapes, and in Float32 everywhere, the single-matrix entry points give the same bits as these.
+ * Routes, in this order:
+ *   m <= 64 and n <= 32      ONE launch, one WAVE per matrix (csrc/dhqr_batched_nrhs.h): the factor and alpha are loaded into
+ *                            registers once, the columns of B_k walk past them in groups of up to four (three for Float64
+ *                            with n > 8, where four do not fit the registers) whose Q'b chains interleave.
+ *                            With profiling on: ONE n_solve group, whatever nrhs and batch.  MEASURED (batch 16384,
+ *                            profiles/batched_nrhs_throughput.txt): the kernel's time goes by groups -- a group costs 2.5 to
+ *                            3.0 single-column solves, a tail's zero columns included -- so against the column loop below
+ *                            nrhs = 2 lost (0.62 - 0.81 x), nrhs = 4 in groups of three lost (0.77 - 0.80 x), nrhs = 4 in
+ *                            groups of four, 8 and 16 won (1.01 - 1.23 x).  The boundary: the kernel runs where its groups
+ *                            carry at least 2.6 real columns on average (5 nrhs >= 13 ceil(nrhs / group)); every other nrhs,
+ *                            nrhs == 1 among them, takes the column loop on the wave-per-matrix single-column kernel: the
+ *                            same bits, nrhs n_solve groups.
+ *   every other shape        (and every shape when the small route is off) ONE EXISTING SOLVE PER COLUMN: a loop r = 0 ..
+ *                            nrhs-1 over dhqr_solve_batched_f64 with b = B + r*ldb and strideb = strideB -- its
+ *                            one-workgroup tier, its serial tier with the synchronisation after every matrix, the profiling
+ *                            counts of nrhs single calls.  Float32: factor, alpha and B are widened ONCE into the Float64
+ *                            workspace, the Float64 entry point of this block runs on them, B is rounded back.
+ *                            A blocked multi-column route for large matrices (Q'B by block reflectors and a triangular
+ *                            solve with a matrix right-hand side) does not exist yet.
+ * nrhs == 0, batch == 0 or n == 0: no-op, DHQR_OK, nothing is touched.  DHQR_EINVAL (nothing is written): everything the
+ * batched family rejects, nrhs < 0, null B or X, ldb < m, strideB < ldb*(nrhs-1) + m, ldx < n, strideX < ldx*(nrhs-1) + n. */
+int32_t dhqr_solve_batched_nrhs_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch);
+int32_t dhqr_ldiv_batched_nrhs_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const double *halpha, int64_t stride_alpha, const double *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, double *hX, int64_t ldx, int64_t strideX, int64_t batch);
+int32_t dhqr_solve_batched_nrhs_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const float *dalpha, int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch);
+int32_t dhqr_ldiv_batched_nrhs_f32(dhqr_ctx *ctx, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const float *halpha, int64_t stride_alpha, const float *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, float *hX, int64_t ldx, int64_t strideX, int64_t batch);
 
 /* KAT hook mirroring partialdot(a, b, lo:hi, Float64) (src:42-49; test/partialdot.jl:18):
  * sum_{i=lo}^{hi-1} da[i]*db[i] (0-based, hi exclusive) reduced on the device with the same

@@ -6,6 +6,10 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
        --dtype f32                                         the Float32 entry points (dhqr_*_f32: native kernels up to 64 x 32,
                                                            the promoted tier beyond), same points, same columns
        --shapes 16x8,32x16                                 only these shapes (default: every shape of SHAPES)
+       --nrhs K [--batches 16384]                          `H_k \\ B_k` with K right-hand sides per matrix instead: ONE
+                                                           dhqr_solve_batched_nrhs_* call against the loop of K
+                                                           dhqr_solve_batched_* calls on the columns (the same resident factor;
+                                                           the same bits, asserted); matrices/s and right-hand sides/s
 
 Per point: 3 warm-up and 10 timed repetitions of (restore the inputs, synchronise, START, calls, synchronise, STOP) on the
 host clock -- a caller's view, launch costs included; median and min-max of matrices per second; the ratio batched / looped
@@ -87,8 +91,89 @@ def point(m, n, batch, dtype="f64"):
     print("POINT " + json.dumps(out), flush=True)
 
 
+def point_nrhs(m, n, batch, nrhs, dtype="f64"):
+    """solve only: the factor stays resident; per repetition B is restored, then ONE multi-column call or K single-column ones"""
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as g
+    pkg = g.import_package()
+    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    os.environ["DHQR_SMALL"] = "1"
+    A = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
+    B0 = pkg.empty_colmajor_batched(batch, m, nrhs, "cuda:0", dtype=tdt)
+    for r in range(nrhs):
+        B0[:, :, r] = pkg.rand_colmajor_batched(batch, m, 1, 7 + 1000 * r, "cuda:0", dtype=tdt).reshape(batch, m)
+    B = B0.clone(memory_format=torch.preserve_format)
+    assert B.stride() == B0.stride() == (m * nrhs, 1, m)
+    H = pkg.qr_batched_(A)
+    al = H.α
+    torch.cuda.synchronize()
+    L = pkg._lib.lib()
+    P = ctypes.c_void_p
+    pa, pal, pb = A.data_ptr(), al.data_ptr(), B.data_ptr()
+    solve_n, solve_1 = getattr(L, f"dhqr_solve_batched_nrhs_{dtype}"), getattr(L, f"dhqr_solve_batched_{dtype}")
+
+    def measure(ctx, fn):
+        rates = []
+        for r in range(WARMUP + REPS):
+            B.copy_(B0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(ctx.handle)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(batch / dt)
+        return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
+
+    def multi(h):
+        pkg._lib.check(solve_n(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), nrhs, m, m * nrhs, batch))
+
+    def columns(h):
+        for r in range(nrhs):
+            pkg._lib.check(solve_1(h, P(pa), m, n, m, m * n, P(pal), n, P(pb + esz * r * m), m * nrhs, batch))
+
+    out = {"m": m, "n": n, "batch": batch, "nrhs": nrhs, "dtype": dtype}
+    ctx = pkg.Context(0)
+    out["nrhs_call"] = measure(ctx, multi)
+    X = B.clone()
+    out["column_loop"] = measure(ctx, columns)
+    ctx.close()
+    assert torch.equal(X, B), "the multi-column call and the loop over the columns must give the same bits"
+    print("POINT " + json.dumps(out), flush=True)
+
+
 def fmt(r):
     return f"{r['median']:12.0f} ({r['min']:.0f} .. {r['max']:.0f})"
+
+
+def main_nrhs(a, shapes, batches):
+    t, K = a.dtype, a.nrhs
+    lines = [f"# tools/batched_bench.py --nrhs {K} --dtype {t}: H_k \\ B_k, {K} right-hand sides per matrix, resident factor; median (min .. max) of 10 repetitions",
+             f"# nrhs call = one dhqr_solve_batched_nrhs_{t}; column loop = {K} x dhqr_solve_batched_{t} on the columns of the same B (the same bits, asserted)"]
+    print("\n".join(lines), flush=True)
+    for (m, n) in shapes:
+        for batch in batches:
+            p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
+                                str(m), str(n), str(batch), "--dtype", t, "--nrhs", str(K)], capture_output=True, text=True)
+            row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
+            if p.returncode != 0 or not row:
+                lines.append(f"{m}x{n} batch {batch} nrhs {K}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
+                print(lines[-1], flush=True)
+                if a.out:
+                    with open(a.out, "w") as f:
+                        f.write("\n".join(lines) + "\n")
+                return 1
+            r = json.loads(row[0][6:])
+            new, old = r["nrhs_call"], r["column_loop"]
+            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} nrhs {K:3d} {t} | nrhs call {fmt(new)} matrices/s {new['median'] * K:13.0f} rhs/s | "
+                   f"column loop {fmt(old)} matrices/s {old['median'] * K:13.0f} rhs/s | nrhs/loop {new['median'] / old['median']:6.2f}x")
+            lines.append(txt)
+            print(txt, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
 
 
 def main():
@@ -97,19 +182,27 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64")
     ap.add_argument("--shapes", default=None, help="e.g. 16x8,32x16 (default: every shape)")
+    ap.add_argument("--nrhs", type=int, default=None, help="right-hand sides per matrix: the multi-column solve against the column loop")
+    ap.add_argument("--batches", default=None, help="e.g. 16384 or 64,1024 (default: every batch of BATCHES)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
     a = ap.parse_args()
     if a.point:
-        point(*a.point, a.dtype)
+        if a.nrhs is not None:
+            point_nrhs(*a.point, a.nrhs, a.dtype)
+        else:
+            point(*a.point, a.dtype)
         return 0
     t = a.dtype
     shapes = SHAPES if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
+    batches = BATCHES if a.batches is None else [int(v) for v in a.batches.split(",")]
+    if a.nrhs is not None:
+        return main_nrhs(a, shapes, batches)
     lines = ["# tools/batched_bench.py: qr! + \\ of `batch` matrices, matrices per second, median (min .. max) of 10 repetitions",
              f"# batched = one dhqr_factor_batched_{t} + one dhqr_solve_batched_{t}; looped = batch x (dhqr_factor_{t} + dhqr_solve_{t}), small route on",
              "# one-CU = the batched calls with DHQR_TUNE batched_wave=0 (one workgroup per matrix) on the wave tier's shapes"]
     print("\n".join(lines), flush=True)
     for (m, n) in shapes:
-        for batch in BATCHES:
+        for batch in batches:
             p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
                                 str(m), str(n), str(batch), "--dtype", t], capture_output=True, text=True)
             row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
