@@ -232,6 +232,14 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
   unsigned char *const prog = reinterpret_cast<unsigned char *>(sync_words + 1);
   unsigned long long *const progall = sync_words + 1;
   int *const broken = reinterpret_cast<int *>(sync_words + 2);
+  // A reflector that is NOT FINITE (a zero column: f = 1 / 0, v = 0 * inf; a NaN or an infinity in the matrix) never enters
+  // vb.  The passes multiply by zero where they have nothing to do -- vr is 0 above row j, d is 0 for the finished columns of
+  // column j's group -- and 0 * NaN is NaN: rows >= j of finished columns (the reflectors stored there) and rows < j of the
+  // columns behind (R) would be lost, where the reference updates rows >= j of the columns > j and nothing else (src:209).
+  // What the reference leaves behind such a column j0 is known without computing it: alpha[j0] as formed, NaN in alpha behind
+  // it and in every entry of rows >= j0 of the columns >= j0, the rest as it stood.  So the builder notes j0 here, hands out
+  // zero reflectors from there on (the passes then change nothing), and the NaN are written with the result.
+  __shared__ int dead_from;  // the first column whose reflector is not finite (0x7fffffff: none)
   const int t = threadIdx.x, w = t >> 6, l = t & 63, rg = l & 15, cs = l >> 4;
   const bool xwave = EXTRA && w == 8;  // holds no part of the matrix
   const int cbase = 4 * w + cs;        // this lane's column of group q: 32 q + cbase (matrix waves)
@@ -254,6 +262,7 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
     sync_words[1] = 0ull;
     sync_words[2] = 0ull;
   }
+  if (t == 0) dead_from = 0x7fffffff;
   // the prologue's hand-over (a step hands over inside its update of the group: see smq_pass_d)
   auto hand_over = [&](int jc) __attribute__((always_inline)) {
     const int q1 = jc / SMQ_GW, cs1 = jc & 3;
@@ -313,6 +322,21 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
       if (row < 16 * NR) vo[row] = row > jn ? x[r] * f : (row == jn ? piv : 0.0);  // src:133-140
     }
     if (l == 0) als[jn] = al;
+    // (uniform: h and s2 come out of readlane, dead_from from one LDS address.  The pivot entry tells: (h - alpha) f is NaN or
+    // infinite whenever s2, f or an entry of the column is not a finite number or the column is zero.  An earlier builder's
+    // dead_from is visible: the barrier, or the acquire of vready, lies between)
+    const bool dead = dead_from < jn;
+    if (dead || !(fabs(piv) <= 1.7976931348623157e308)) {
+#pragma unroll
+      for (int r = 0; r < RBL; ++r)
+        if (l + 64 * r < 16 * NR) vo[l + 64 * r] = 0.0;
+      if (l == 0) {
+        if (dead)
+          als[jn] = __builtin_nan("");
+        else
+          dead_from = jn;
+      }
+    }
   };
   auto step = [&](auto r0c, int j) __attribute__((always_inline)) {
     constexpr int R0 = decltype(r0c)::value;
@@ -411,6 +435,18 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
       for (int r = 0; r < NR; ++r) {
         const int row = rg + 16 * r;
         if (row < m && col < n) Adst[(int64_t)row + (int64_t)col * ldd] = a[q][r];
+      }
+    }
+  }
+  if (dead_from < n && !xwave) {  // (uniform; every barrier of the column loop, or the one above, lies behind the builder's store)
+    const int j0 = dead_from;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int col = SMQ_GW * q + cbase;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int row = rg + 16 * r;
+        if (row < m && col < n && row >= j0 && col >= j0) Adst[(int64_t)row + (int64_t)col * ldd] = __builtin_nan("");
       }
     }
   }
