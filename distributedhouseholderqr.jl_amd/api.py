@@ -566,16 +566,9 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
         return H
     if not isinstance(A, np.ndarray) or A.dtype not in (np.float64, np.float32):
         raise TypeError("float64 or float32 numpy array or CUDA tensor expected")
-    lay = None
-    if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
-        lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
-    F = A
-    if lay is None:
-        F = np.empty((batch, n, m), dtype=A.dtype).transpose(0, 2, 1)
-        F[...] = A
-        lay = (max(m, 1), max(m * n, 1))
+    F, lda, strideA = _host_batch(A)
     H = DistributedHouseholderQRStruct(A)
-    check(qr(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+    check(qr(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lda, strideA,
                                 H.α.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch, nb))
     if F is not A:
         A[...] = F
@@ -669,18 +662,11 @@ def ldiv_batched(H: DistributedHouseholderQRStruct, b):
                                        ctypes.c_void_p(α.data_ptr()), max(n, 1), ctypes.c_void_p(w.data_ptr()), max(m, 1), batch))
         ctx.synchronize()
         return w[:, :n].clone()
-    lay = None
-    if all(st % A.itemsize == 0 and st >= 0 for st in A.strides):
-        lay = _batch_layout(A.shape, tuple(st // A.itemsize for st in A.strides))
-    F = A
-    if lay is None:
-        F = np.empty((batch, n, m), dtype=A.dtype).transpose(0, 2, 1)
-        F[...] = A
-        lay = (max(m, 1), max(m * n, 1))
+    F, lda, strideA = _host_batch(A)
     al, sal = _host_rows(α, batch, n, "α", A.dtype)
     bb, sb = _host_rows(b, batch, m, "b", A.dtype)
     x = np.empty((batch, n), dtype=A.dtype)
-    check(ldiv_(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lay[0], lay[1],
+    check(ldiv_(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lda, strideA,
                                   al.ctypes.data_as(ctypes.c_void_p), sal, bb.ctypes.data_as(ctypes.c_void_p), sb,
                                   x.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch))
     return x

@@ -1272,6 +1272,8 @@ static int32_t apply_q_impl(dhqr_ctx *c, const double *dA, int64_t m, int64_t n,
   return DHQR_OK;
 }
 
+#include "dhqr_batched_host.h"
+
 // =================================================================================== C ABI
 extern "C" {
 
@@ -1985,330 +1987,47 @@ int32_t dhqr_ldiv_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
   return rc;
 }
 
-// ---- batches of small matrices (dhqr.h: dhqr_factor_batched_f64 ...) ------------------------------------------------
-// Tiers by shape: one wave per matrix (dhqr_batched.h) | the single-workgroup kernels of dhqr_small.h with grid = batch, in
-// their barrier form | a host loop over the single-matrix drivers.
-static int32_t check_batch(const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
-                           int64_t stride_alpha, int64_t batch) {
-  CHECK(check_mat(A, m, n, lda, true));
-  if (!alpha) return set_err(DHQR_EINVAL, "null alpha pointer");
-  if (strideA < lda * (n - 1) + m)
-    return set_err(DHQR_EINVAL, "strideA %lld < lda*(n-1)+m = %lld", (long long)strideA, (long long)(lda * (n - 1) + m));
-  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
-  if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
-  return DHQR_OK;
-}
-static inline bool batched_wave_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
-  return c->small_route && c->batched_wave && m <= BQW_MAX_M && n <= BQW_MAX_N && n >= 1 && m >= n;
-}
-
+// ---- batches of small matrices, Float32, several right-hand sides per matrix (dhqr.h: dhqr_factor_batched_f64 ...) -------
+// The host side -- argument rules, tiers, staging -- is dhqr_batched_host.h, once for both element types; the kernels are
+// dhqr_batched.h, dhqr_f32.h, dhqr_batched_nrhs.h and dhqr_small.h.
 int32_t dhqr_factor_batched_f64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
                                 int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  if (nb != 0 && nb != DHQR_NB)
-    return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
-  const bool wave = batched_wave_fit(c, m, n);
-  const int fit = small_qr_fit(c, m, n);
-  if (!wave && fit < 0) {  // serial: one single-matrix factorisation after the other
-    // (and synchronised after each: the error word of the drivers' bounded waits belongs to one call at a time, dhqr.h)
-    for (int64_t k = 0; k < batch; ++k) {
-      CHECK(dhqr_factor_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, nb));
-      HIPCHECK(hipStreamSynchronize(c->stream));
-      CHECK(pipe_error_check(c));
-    }
-    return DHQR_OK;
-  }
-  c->tc_valid = false;  // whatever was kept for one of these matrices is gone
-  c->retry.valid = false;
-  CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
-  if (wave) {
-    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-    if (n <= 8)
-      hipLaunchKernelGGL((k_batched_qr_wave<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    else if (n <= 16)
-      hipLaunchKernelGGL((k_batched_qr_wave<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    else
-      hipLaunchKernelGGL((k_batched_qr_wave<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    LAUNCHCHECK();
-  } else {
-    // the barrier form for every fit: with a batch in flight the compute units are full either way, and the barrier form
-    // has no bounded wait that could give up (same bits as the flag form)
-    SmallBatch sb;
-    sb.batch = batch;
-    sb.strideA = strideA;
-    sb.stride_alpha = stride_alpha;
-    const int keep = c->small_flags;
-    c->small_flags = 0;
-    const int32_t rc = small_qr_launch_strided(c, fit, dA, lda, dA, lda, m, n, dalpha, nullptr, 0, sb);
-    c->small_flags = keep;
-    CHECK(rc);
-  }
-  if (c->profiling)
-    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 16.0 * (double)(m - j) * (double)(n - j - 1);
-  return prof_end(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, &nb);
+  return factor_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nb);
 }
 
 int32_t dhqr_solve_batched_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                const double *dalpha, int64_t stride_alpha, double *db, int64_t strideb, int64_t batch) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  if (!db) return set_err(DHQR_EINVAL, "null b pointer");
-  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
-  const bool wave = batched_wave_fit(c, m, n);
-  if (!wave && !small_ldiv_fit(c, m, n)) {
-    for (int64_t k = 0; k < batch; ++k) {  // (a solve's repetition, pipe_error_check, knows the last solve only)
-      CHECK(dhqr_solve_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, db + k * strideb));
-      HIPCHECK(hipStreamSynchronize(c->stream));
-      CHECK(pipe_error_check(c));
-    }
-    return DHQR_OK;
-  }
-  CHECK(prof_begin(c, CAT_SOLVE));
-  if (wave) {
-    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-    if (n <= 8)
-      hipLaunchKernelGGL((k_batched_ldiv_wave<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    else if (n <= 16)
-      hipLaunchKernelGGL((k_batched_ldiv_wave<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    else
-      hipLaunchKernelGGL((k_batched_ldiv_wave<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    LAUNCHCHECK();
-  } else {
-    SmallBatch sb;
-    sb.batch = batch;
-    sb.strideA = strideA;
-    sb.stride_alpha = stride_alpha;
-    sb.strideb = strideb;
-    CHECK(small_ldiv_launch(c, dA, lda, m, n, dalpha, db, db, nullptr, nullptr, nullptr, 0, sb));  // (the factor is in HBM: no Awork)
-  }
-  return prof_end(c);
-}
-
-// host <-> device copies of `batch` blocks of rows x cols doubles: block k at h + k hstride (leading dimension hld) and at
-// d + k rows cols (packed)
-static int32_t batch_copy(dhqr_ctx *c, double *d, const double *h, int64_t rows, int64_t cols, int64_t hld, int64_t hstride,
-                          int64_t batch, bool up) {
-  auto copy2d = [&](double *dp, const double *hp, int64_t dpitch, int64_t hpitch, int64_t width, int64_t height) -> int32_t {
-    if (up)
-      HIPCHECK(hipMemcpy2DAsync(dp, dpitch * sizeof(double), hp, hpitch * sizeof(double), width * sizeof(double), height,
-                                hipMemcpyHostToDevice, c->stream));
-    else
-      HIPCHECK(hipMemcpy2DAsync(const_cast<double *>(hp), hpitch * sizeof(double), dp, dpitch * sizeof(double),
-                                width * sizeof(double), height, hipMemcpyDeviceToHost, c->stream));
-    return DHQR_OK;
-  };
-  if (hld == rows || cols == 1) return copy2d(d, h, rows * cols, hstride, rows * cols, batch);  // every block contiguous
-  if (hstride == hld * cols) return copy2d(d, h, rows, hld, rows, cols * batch);               // one column pitch throughout
-  for (int64_t k = 0; k < batch; ++k) CHECK(copy2d(d + k * rows * cols, h + k * hstride, rows, hld, rows, cols));
-  return DHQR_OK;
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_column(db, m, strideb));
+  return solve_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch);
 }
 
 int32_t dhqr_qr_batched_f64(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
                             int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  if (nb != 0 && nb != DHQR_NB)
-    return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->batch_dev, na + nal));
-  double *dA = c->batch_dev.p, *dal = dA + na;
-  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
-  int32_t rc = dhqr_factor_batched_f64(c, dA, m, n, m, m * n, dal, n, batch, nb);
-  if (rc == DHQR_OK) rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, false);
-  if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, false);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);
-  return rc;
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, &nb);
+  return qr_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, batch, nb, BATCH);
 }
 
 int32_t dhqr_ldiv_batched_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                               const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
                               int64_t stridex, int64_t batch) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  if (!hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
-  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
-  if (stridex < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)stridex, (long long)n);
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->batch_dev, na + nal + (size_t)m * (size_t)batch));
-  double *dA = c->batch_dev.p, *dal = dA + na, *db = dal + nal;
-  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
-  CHECK(batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
-  CHECK(batch_copy(c, db, hb, m, 1, m, strideb, batch, true));  // src:318 copy of b
-  int32_t rc = dhqr_solve_batched_f64(c, dA, m, n, m, m * n, dal, n, db, m, batch);
-  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);  // (the serial tier's solves may have been repeated: dhqr.h)
-  if (rc == DHQR_OK)  // src:320: x_k = the first n entries of b_k
-    HIPCHECK(hipMemcpy2DAsync(hx, stridex * sizeof(double), db, m * sizeof(double), n * sizeof(double), batch,
-                              hipMemcpyDeviceToHost, c->stream));
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  return rc;
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_column(hb, m, strideb),
+                rhs_column(hx, n, stridex));
+  return ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hb, 1, m, strideb, hx, n, stridex, batch, BATCH, ONE_COLUMN);
 }
 
-// ---- Float32 (dhqr.h: dhqr_factor_f32 ...) -----------------------------------------------------------------------------
-// Two tiers: m <= 64 and n <= 32 with the small route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single
-// matrix is a batch of 1) --, everything else PROMOTED: widened into a Float64 workspace of the context (packed: lda = m,
-// matrix k at k m n), the Float64 entry point with the caller's nb, rounded back.  `single`: the promoted tier calls
-// dhqr_factor_f64 / dhqr_solve_f64 (else the batched entry points).
-static int32_t f32_convert_launch(dhqr_ctx *c, bool widen, const void *src, int64_t lds, int64_t sstride, void *dst, int64_t ldd,
-                                  int64_t dstride, int64_t rows, int64_t cols, int64_t batch) {
-  const int64_t total = rows * cols * batch;
-  if (total <= 0) return DHQR_OK;
-  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-  if (widen)
-    hipLaunchKernelGGL(k_widen_f32, dim3(grid), dim3(256), 0, c->stream, (const float *)src, lds, sstride, (double *)dst, ldd, dstride,
-                       rows, cols, batch);
-  else
-    hipLaunchKernelGGL(k_round_f32, dim3(grid), dim3(256), 0, c->stream, (const double *)src, lds, sstride, (float *)dst, ldd, dstride,
-                       rows, cols, batch);
-  LAUNCHCHECK();
-  return DHQR_OK;
-}
-
-static inline size_t f32_even(size_t n) { return (n + 1) & ~(size_t)1; }
-
-static int32_t f32_factor(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
-                          int64_t stride_alpha, int64_t batch, int32_t nb, bool single) {
-  if (batched_wave_fit(c, m, n)) {
-    // (tc_valid / retry stay: what they remember are Float64 buffers, which a Float32 factorisation cannot overwrite -- the
-    // promoted tier's workspace goes through dhqr_factor_f64, which resets them itself)
-    CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
-    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-    if (n <= 8)
-      hipLaunchKernelGGL((k_batched_qr_wave_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    else if (n <= 16)
-      hipLaunchKernelGGL((k_batched_qr_wave_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    else
-      hipLaunchKernelGGL((k_batched_qr_wave_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-    LAUNCHCHECK();
-    if (c->profiling)
-      for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 8.0 * (double)(m - j) * (double)(n - j - 1);
-    return prof_end(c);
-  }
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->f32_ws, f32_even(na) + nal));
-  double *wA = c->f32_ws.p, *wal = wA + f32_even(na);  // (sections on 16-byte boundaries, like separately allocated arrays)
-  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
-  // synchronous where the Float64 route is: the blocked driver of a single matrix, the serial tier of a batch
-  const bool sync = small_qr_fit(c, m, n) < 0 && (!single || nb != 0);
-  CHECK(single ? dhqr_factor_f64(c, wA, m, n, m, wal, nb) : dhqr_factor_batched_f64(c, wA, m, n, m, m * n, wal, n, batch, nb));
-  CHECK(f32_convert_launch(c, false, wA, m, m * n, dA, lda, strideA, m, n, batch));
-  CHECK(f32_convert_launch(c, false, wal, n, n, dalpha, n, stride_alpha, n, 1, batch));
-  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
-  return DHQR_OK;
-}
-
-static int32_t f32_solve(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
-                         int64_t stride_alpha, float *db, int64_t strideb, int64_t batch, bool single) {
-  if (batched_wave_fit(c, m, n)) {
-    CHECK(prof_begin(c, CAT_SOLVE));
-    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-    if (n <= 8)
-      hipLaunchKernelGGL((k_batched_ldiv_wave_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    else if (n <= 16)
-      hipLaunchKernelGGL((k_batched_ldiv_wave_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    else
-      hipLaunchKernelGGL((k_batched_ldiv_wave_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-    LAUNCHCHECK();
-    return prof_end(c);
-  }
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->f32_ws, f32_even(na) + f32_even(nal) + (size_t)m * (size_t)batch));
-  double *wA = c->f32_ws.p, *wal = wA + f32_even(na), *wb = wal + f32_even(nal);
-  if (c->tc_A == wA) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
-  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
-  CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, wal, n, n, n, 1, batch));
-  CHECK(f32_convert_launch(c, true, db, m, strideb, wb, m, m, m, 1, batch));
-  const bool sync = !single && !small_ldiv_fit(c, m, n);  // (the serial tier of a batch)
-  CHECK(single ? dhqr_solve_f64(c, wA, m, n, m, wal, wb) : dhqr_solve_batched_f64(c, wA, m, n, m, m * n, wal, n, wb, m, batch));
-  if (single && c->retry.valid && c->retry.b == wb) {  // (a flag left by an earlier Float64 solve names another b)
-    // THIS solve took the persistent Q'b kernel and may be REPEATED by the next synchronising entry point (dhqr.h:
-    // dhqr_get_solve_retries) -- into the workspace, behind the rounding enqueued below.  Settle it first; afterwards nothing
-    // may come back to the remembered pointers: they lie in a workspace that a later call may reallocate.
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    const int32_t rc = pipe_error_check(c);
-    c->retry.valid = false;
-    CHECK(rc);
-  }
-  CHECK(f32_convert_launch(c, false, wb, m, m, db, m, strideb, m, 1, batch));
-  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
-  return DHQR_OK;
-}
-
-// packed device staging of the host forms, in floats: matrices | alphas | right-hand sides
-static int32_t f32_dev_ensure(dhqr_ctx *c, size_t nfloats) { return ensure(c, c->f32_dev, (nfloats + 1) / 2); }
-// host <-> device copies of `batch` blocks of rows x cols floats (batch_copy for Float32)
-static int32_t batch_copy_f32(dhqr_ctx *c, float *d, const float *h, int64_t rows, int64_t cols, int64_t hld, int64_t hstride,
-                              int64_t batch, bool up) {
-  auto copy2d = [&](float *dp, const float *hp, int64_t dpitch, int64_t hpitch, int64_t width, int64_t height) -> int32_t {
-    if (up)
-      HIPCHECK(hipMemcpy2DAsync(dp, dpitch * sizeof(float), hp, hpitch * sizeof(float), width * sizeof(float), height,
-                                hipMemcpyHostToDevice, c->stream));
-    else
-      HIPCHECK(hipMemcpy2DAsync(const_cast<float *>(hp), hpitch * sizeof(float), dp, dpitch * sizeof(float), width * sizeof(float),
-                                height, hipMemcpyDeviceToHost, c->stream));
-    return DHQR_OK;
-  };
-  if (hld == rows || cols == 1) return copy2d(d, h, rows * cols, hstride, rows * cols, batch);  // every block contiguous
-  if (hstride == hld * cols) return copy2d(d, h, rows, hld, rows, cols * batch);               // one column pitch throughout
-  for (int64_t k = 0; k < batch; ++k) CHECK(copy2d(d + k * rows * cols, h + k * hstride, rows, hld, rows, cols));
-  return DHQR_OK;
-}
-
-static int32_t f32_qr_host(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
-                           int64_t stride_alpha, int64_t batch, int32_t nb, bool single) {
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(f32_dev_ensure(c, na + nal));
-  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na;
-  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
-  int32_t rc = f32_factor(c, dA, m, n, m, m * n, dal, n, batch, nb, single);
-  if (rc == DHQR_OK) rc = batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, false);
-  if (rc == DHQR_OK) rc = batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, false);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);
-  return rc;
-}
-
-static int32_t f32_ldiv_host(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *halpha,
-                             int64_t stride_alpha, const float *hb, int64_t strideb, float *hx, int64_t stridex, int64_t batch,
-                             bool single) {
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(f32_dev_ensure(c, na + nal + (size_t)m * (size_t)batch));
-  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na, *db = dal + nal;
-  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
-  CHECK(batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
-  CHECK(batch_copy_f32(c, db, hb, m, 1, m, strideb, batch, true));  // src:318 copy of b
-  int32_t rc = f32_solve(c, dA, m, n, m, m * n, dal, n, db, m, batch, single);
-  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);
-  if (rc == DHQR_OK)  // src:320: x_k = the first n entries of b_k
-    HIPCHECK(hipMemcpy2DAsync(hx, stridex * sizeof(float), db, m * sizeof(float), n * sizeof(float), batch, hipMemcpyDeviceToHost,
-                              c->stream));
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  return rc;
-}
-
-static int32_t check_nb(int32_t nb) {
-  if (nb != 0 && nb != DHQR_NB) return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
-  return DHQR_OK;
-}
-
+// Float32, one matrix: a batch of 1 (stride lda*(n-1)+m: exactly the matrix)
 int32_t dhqr_factor_f32(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, float *dalpha, int32_t nb) {
   ENTER(c);
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(dA, m, n, lda, true));
   if (!dalpha) return set_err(DHQR_EINVAL, "null alpha pointer");
   CHECK(check_nb(nb));
-  return f32_factor(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, 1, nb, true);
+  return factor_batched(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, 1, nb, SINGLE);
 }
 
 int32_t dhqr_qr_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, float *halpha, int32_t nb) {
@@ -2317,7 +2036,7 @@ int32_t dhqr_qr_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, f
   CHECK(check_mat(hA, m, n, lda, true));
   if (!halpha) return set_err(DHQR_EINVAL, "null alpha pointer");
   CHECK(check_nb(nb));
-  return f32_qr_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, 1, nb, true);
+  return qr_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, 1, nb, SINGLE);
 }
 
 int32_t dhqr_solve_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, const float *dalpha, float *db) {
@@ -2325,7 +2044,7 @@ int32_t dhqr_solve_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(dA, m, n, lda, true));
   if (!dalpha || !db) return set_err(DHQR_EINVAL, "null alpha or b pointer");
-  return f32_solve(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, db, m, 1, true);
+  return solve_batched(c, dA, m, n, lda, lda * (n - 1) + m, dalpha, n, db, m, 1, SINGLE);
 }
 
 int32_t dhqr_ldiv_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, const float *halpha, const float *hb,
@@ -2334,218 +2053,71 @@ int32_t dhqr_ldiv_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(hA, m, n, lda, true));
   if (!halpha || !hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
-  return f32_ldiv_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, hb, m, hx, n, 1, true);
+  return ldiv_host(c, hA, m, n, lda, lda * (n - 1) + m, halpha, n, hb, 1, m, m, hx, n, n, 1, SINGLE, ONE_COLUMN);
 }
 
 int32_t dhqr_factor_batched_f32(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
                                 int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  CHECK(check_nb(nb));
-  return f32_factor(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nb, false);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, &nb);
+  return factor_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nb, BATCH);
 }
 
 int32_t dhqr_solve_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                const float *dalpha, int64_t stride_alpha, float *db, int64_t strideb, int64_t batch) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  if (!db) return set_err(DHQR_EINVAL, "null b pointer");
-  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
-  return f32_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch, false);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_column(db, m, strideb));
+  return solve_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch, BATCH);
 }
 
 int32_t dhqr_qr_batched_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
                             int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  CHECK(check_nb(nb));
-  return f32_qr_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, batch, nb, false);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, &nb);
+  return qr_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, batch, nb, BATCH);
 }
 
 int32_t dhqr_ldiv_batched_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                               const float *halpha, int64_t stride_alpha, const float *hb, int64_t strideb, float *hx,
                               int64_t stridex, int64_t batch) {
   ENTER(c);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  if (batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  if (!hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
-  if (strideb < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)strideb, (long long)m);
-  if (stridex < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)stridex, (long long)n);
-  return f32_ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hb, strideb, hx, stridex, batch, false);
-}
-
-// ---- several right-hand sides per matrix (dhqr.h: dhqr_solve_batched_nrhs_f64 ...) ------------------------------------
-// The wave tier: ONE launch of the multi-column kernels of dhqr_batched_nrhs.h.  Every other shape: the existing
-// single-column entry point, column by column -- its tiers, its synchronisation, its profiling counts, its bits.
-// Does the multi-column kernel pay?  Measured (profiles/batched_nrhs_throughput.txt, batch 16384): the kernel is bound by
-// instruction issue, not by re-reading the matrix, and its time goes by GROUPS -- a group of rg chains costs 2.5 to 3.0
-// single-column solves whether its columns are real or the zeros of a tail.  nrhs = 2 loses everywhere (0.62 - 0.81 x the
-// column loop), nrhs = 4 in groups of three (Float64, n > 8) loses (0.77 - 0.80 x); nrhs = 4 in groups of four, 8 and 16 win
-// (1.01 - 1.23 x).  So: the kernel where the groups carry at least 2.6 real columns on average, the column loop -- the
-// same bits -- elsewhere.
-static inline bool nrhs_wave_pays(int64_t nrhs, int rg) {
-  const int64_t groups = (nrhs + rg - 1) / rg;
-  return 5 * nrhs >= 13 * groups;
-}
-static int32_t check_nrhs_sizes(int64_t nrhs, int64_t batch) {
-  if (nrhs < 0) return set_err(DHQR_EINVAL, "negative nrhs %lld", (long long)nrhs);
-  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
-  return DHQR_OK;
-}
-static int32_t check_nrhs(const void *B, const char *name, int64_t rows, int64_t nrhs, int64_t ldb, int64_t strideB) {
-  if (!B) return set_err(DHQR_EINVAL, "null %s pointer", name);
-  if (nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "nrhs %lld too large", (long long)nrhs);
-  if (ldb < rows) return set_err(DHQR_EINVAL, "leading dimension of %s %lld < %lld", name, (long long)ldb, (long long)rows);
-  if (strideB < ldb * (nrhs - 1) + rows)
-    return set_err(DHQR_EINVAL, "stride of %s %lld < ld*(nrhs-1)+rows = %lld", name, (long long)strideB,
-                   (long long)(ldb * (nrhs - 1) + rows));
-  return DHQR_OK;
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_column(hb, m, strideb),
+                rhs_column(hx, n, stridex));
+  return ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hb, 1, m, strideb, hx, n, stridex, batch, BATCH, ONE_COLUMN);
 }
 
 int32_t dhqr_solve_batched_nrhs_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                     const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb,
                                     int64_t strideB, int64_t batch) {
   ENTER(c);
-  CHECK(check_nrhs_sizes(nrhs, batch));
-  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  CHECK(check_nrhs(dB, "B", m, nrhs, ldb, strideB));
-  if (!batched_wave_fit(c, m, n) || !nrhs_wave_pays(nrhs, n <= 8 ? BQN_RG_D(8) : BQN_RG_D(32))) {
-    for (int64_t r = 0; r < nrhs; ++r)
-      CHECK(dhqr_solve_batched_f64(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
-    return DHQR_OK;
-  }
-  CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
-  const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-  if (n <= 8)
-    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-  else if (n <= 16)
-    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-  else
-    hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-  LAUNCHCHECK();
-  return prof_end(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_block(dB, nrhs, ldb, strideB));
+  return solve_batched_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
 }
 
 int32_t dhqr_ldiv_batched_nrhs_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                    const double *halpha, int64_t stride_alpha, const double *hB, int64_t nrhs, int64_t ldb,
                                    int64_t strideB, double *hX, int64_t ldx, int64_t strideX, int64_t batch) {
   ENTER(c);
-  CHECK(check_nrhs_sizes(nrhs, batch));
-  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  CHECK(check_nrhs(hB, "B", m, nrhs, ldb, strideB));
-  CHECK(check_nrhs(hX, "X", n, nrhs, ldx, strideX));
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->batch_dev, na + nal + (size_t)m * (size_t)nrhs * (size_t)batch));
-  double *dA = c->batch_dev.p, *dal = dA + na, *dB = dal + nal;
-  CHECK(batch_copy(c, dA, hA, m, n, lda, strideA, batch, true));
-  CHECK(batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
-  CHECK(batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true));  // src:318 copy of B
-  int32_t rc = dhqr_solve_batched_nrhs_f64(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch);
-  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);  // (the serial tier's solves may have been repeated: dhqr.h)
-  if (rc == DHQR_OK) {  // src:320: X_k = the first n rows of B_k
-    if (strideX == ldx * nrhs || batch == 1) {  // one column pitch throughout
-      if (hipMemcpy2DAsync(hX, ldx * sizeof(double), dB, m * sizeof(double), n * sizeof(double), nrhs * batch, hipMemcpyDeviceToHost,
-                           c->stream) != hipSuccess)
-        rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
-    } else {
-      for (int64_t k = 0; k < batch && rc == DHQR_OK; ++k)  // (a failed enqueue still reaches the synchronisation below)
-        if (hipMemcpy2DAsync(hX + k * strideX, ldx * sizeof(double), dB + k * m * nrhs, m * sizeof(double), n * sizeof(double),
-                             nrhs, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-          rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
-    }
-  }
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  return rc;
-}
-
-// Float32: the native multi-column kernel on the wave tier; everything else PROMOTED once -- factor, alpha and all of B
-// widened into the Float64 workspace, the Float64 entry point above, B rounded back.
-static int32_t f32_solve_nrhs(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
-                              int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
-  if (batched_wave_fit(c, m, n) && !nrhs_wave_pays(nrhs, BQN_RG)) {  // the native single-column kernel, column by column
-    for (int64_t r = 0; r < nrhs; ++r)
-      CHECK(f32_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch, false));
-    return DHQR_OK;
-  }
-  if (batched_wave_fit(c, m, n)) {
-    CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
-    const dim3 grid((unsigned)((batch + BQW_WAVES - 1) / BQW_WAVES)), block(64 * BQW_WAVES);
-    if (n <= 8)
-      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<8>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-    else if (n <= 16)
-      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<16>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-    else
-      hipLaunchKernelGGL((k_batched_ldiv_wave_nrhs_s<32>), grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
-    LAUNCHCHECK();
-    return prof_end(c);
-  }
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(ensure(c, c->f32_ws, f32_even(na) + f32_even(nal) + (size_t)m * (size_t)nrhs * (size_t)batch));
-  double *wA = c->f32_ws.p, *wal = wA + f32_even(na), *wB = wal + f32_even(nal);
-  if (c->tc_A == wA) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
-  CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
-  CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, wal, n, n, n, 1, batch));
-  CHECK(f32_convert_launch(c, true, dB, ldb, strideB, wB, m, m * nrhs, m, nrhs, batch));
-  const bool sync = !small_ldiv_fit(c, m, n);  // (the serial tier)
-  CHECK(dhqr_solve_batched_nrhs_f64(c, wA, m, n, m, m * n, wal, n, wB, nrhs, m, m * nrhs, batch));
-  CHECK(f32_convert_launch(c, false, wB, m, m * nrhs, dB, ldb, strideB, m, nrhs, batch));
-  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
-  return DHQR_OK;
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB),
+                rhs_block(hX, nrhs, ldx, strideX));
+  return ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hB, nrhs, ldb, strideB, hX, ldx, strideX, batch, BATCH, MULTI_COLUMN);
 }
 
 int32_t dhqr_solve_batched_nrhs_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                     const float *dalpha, int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb,
                                     int64_t strideB, int64_t batch) {
   ENTER(c);
-  CHECK(check_nrhs_sizes(nrhs, batch));
-  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(dA, m, n, lda, strideA, dalpha, stride_alpha, batch));
-  CHECK(check_nrhs(dB, "B", m, nrhs, ldb, strideB));
-  return f32_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_block(dB, nrhs, ldb, strideB));
+  return solve_batched_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
 }
 
 int32_t dhqr_ldiv_batched_nrhs_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                    const float *halpha, int64_t stride_alpha, const float *hB, int64_t nrhs, int64_t ldb,
                                    int64_t strideB, float *hX, int64_t ldx, int64_t strideX, int64_t batch) {
   ENTER(c);
-  CHECK(check_nrhs_sizes(nrhs, batch));
-  if (nrhs == 0 || batch == 0 || no_columns(m, n)) return DHQR_OK;
-  CHECK(check_batch(hA, m, n, lda, strideA, halpha, stride_alpha, batch));
-  CHECK(check_nrhs(hB, "B", m, nrhs, ldb, strideB));
-  CHECK(check_nrhs(hX, "X", n, nrhs, ldx, strideX));
-  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  CHECK(f32_dev_ensure(c, na + nal + (size_t)m * (size_t)nrhs * (size_t)batch));
-  float *dA = reinterpret_cast<float *>(c->f32_dev.p), *dal = dA + na, *dB = dal + nal;
-  CHECK(batch_copy_f32(c, dA, hA, m, n, lda, strideA, batch, true));
-  CHECK(batch_copy_f32(c, dal, halpha, n, 1, n, stride_alpha, batch, true));
-  CHECK(batch_copy_f32(c, dB, hB, m, nrhs, ldb, strideB, batch, true));  // src:318 copy of B
-  int32_t rc = f32_solve_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch);
-  if (rc == DHQR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  if (rc == DHQR_OK) rc = pipe_error_check(c);
-  if (rc == DHQR_OK) {  // src:320: X_k = the first n rows of B_k
-    if (strideX == ldx * nrhs || batch == 1) {  // one column pitch throughout
-      if (hipMemcpy2DAsync(hX, ldx * sizeof(float), dB, m * sizeof(float), n * sizeof(float), nrhs * batch, hipMemcpyDeviceToHost,
-                           c->stream) != hipSuccess)
-        rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
-    } else {
-      for (int64_t k = 0; k < batch && rc == DHQR_OK; ++k)  // (a failed enqueue still reaches the synchronisation below)
-        if (hipMemcpy2DAsync(hX + k * strideX, ldx * sizeof(float), dB + k * m * nrhs, m * sizeof(float), n * sizeof(float), nrhs,
-                             hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-          rc = set_err(DHQR_EHIP, "hipMemcpy2DAsync of X failed");
-    }
-  }
-  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
-  return rc;
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB),
+                rhs_block(hX, nrhs, ldx, strideX));
+  return ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hB, nrhs, ldb, strideB, hX, ldx, strideX, batch, BATCH, MULTI_COLUMN);
 }
 
 int32_t dhqr_partialdot_f64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,

@@ -1,0 +1,398 @@
+// dhqr_batched_host.h -- the host side of the small-matrix entry points (dhqr.h: dhqr_factor_batched_f64 ...
+// dhqr_ldiv_batched_nrhs_f32, and the Float32 single-matrix forms), written once for T = double and T = float.  Host code
+// only; included by dhqr_api.hip ahead of its extern "C" block (templates need C++ linkage), which keeps the exported
+// functions themselves: ENTER, the argument check, one call into this file.
+// Tiers by shape.  Float64: one wave per matrix (dhqr_batched.h) | the single-workgroup kernels of dhqr_small.h with grid =
+// batch, in their barrier form | a host loop over the single-matrix drivers.  Float32: m <= 64 and n <= 32 with the small
+// route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single matrix is a batch of 1) --, everything else
+// PROMOTED: widened into a Float64 workspace of the context, the Float64 route with the caller's nb, rounded back.
+// The host forms (qr_host, ldiv_host) end alike: after a failure of any step they still reach the final
+// hipStreamSynchronize -- nothing is left in flight on the caller's arrays -- and return the FIRST error.  (Before, the
+// single-column ldiv forms returned from a failed enqueue of the copy of X without it.)
+#pragma once
+#include <type_traits>
+
+static int32_t pipe_error_check(dhqr_ctx *c);  // (dhqr_api.hip, below this file's inclusion)
+
+// ---- argument checks -----------------------------------------------------------------------------------------------------
+static int32_t check_nb(int32_t nb) {
+  if (nb != 0 && nb != DHQR_NB) return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
+  return DHQR_OK;
+}
+static int32_t check_batch(const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
+                           int64_t stride_alpha, int64_t batch) {
+  CHECK(check_mat(A, m, n, lda, true));
+  if (!alpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  if (strideA < lda * (n - 1) + m)
+    return set_err(DHQR_EINVAL, "strideA %lld < lda*(n-1)+m = %lld", (long long)strideA, (long long)(lda * (n - 1) + m));
+  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
+  if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
+  return DHQR_OK;
+}
+static int32_t check_nrhs(const void *B, const char *name, int64_t rows, int64_t nrhs, int64_t ldb, int64_t strideB) {
+  if (!B) return set_err(DHQR_EINVAL, "null %s pointer", name);
+  if (nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "nrhs %lld too large", (long long)nrhs);
+  if (ldb < rows) return set_err(DHQR_EINVAL, "leading dimension of %s %lld < %lld", name, (long long)ldb, (long long)rows);
+  if (strideB < ldb * (nrhs - 1) + rows)
+    return set_err(DHQR_EINVAL, "stride of %s %lld < ld*(nrhs-1)+rows = %lld", name, (long long)strideB,
+                   (long long)(ldb * (nrhs - 1) + rows));
+  return DHQR_OK;
+}
+// The right-hand sides (or solutions) of a batched call as its checker sees them: rows x nrhs elements per matrix, leading
+// dimension ld, matrix k at p + k stride.  column: one per matrix (b / x of the single-column forms: nrhs = 1, ld = rows).
+struct RhsArg {
+  const void *p = nullptr;
+  int64_t nrhs = 1, ld = 0, stride = 0;
+  bool block = false, given = false;
+};
+static inline RhsArg rhs_column(const void *p, int64_t rows, int64_t stride) { return RhsArg{p, 1, rows, stride, false, true}; }
+static inline RhsArg rhs_block(const void *p, int64_t nrhs, int64_t ld, int64_t stride) { return RhsArg{p, nrhs, ld, stride, true, true}; }
+// The preamble of every batched entry point.  What the call has beside A and alpha: nb (qr!) | B (a solve on the device) |
+// B and X (a solve on the host), both columns or both blocks.
+// *empty: nothing to do (batch, n or nrhs is 0) -- and then no pointer, leading dimension or stride has been looked at.
+static int32_t check_batched(bool *empty, const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
+                             int64_t stride_alpha, int64_t batch, const int32_t *nb, RhsArg B = RhsArg(), RhsArg X = RhsArg()) {
+  if (B.block && B.nrhs < 0) return set_err(DHQR_EINVAL, "negative nrhs %lld", (long long)B.nrhs);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  *empty = (B.block && B.nrhs == 0) || batch == 0 || no_columns(m, n);
+  if (*empty) return DHQR_OK;
+  CHECK(check_batch(A, m, n, lda, strideA, alpha, stride_alpha, batch));
+  if (nb) return check_nb(*nb);
+  if (B.block) {
+    CHECK(check_nrhs(B.p, "B", m, B.nrhs, B.ld, B.stride));
+    return X.given ? check_nrhs(X.p, "X", n, X.nrhs, X.ld, X.stride) : DHQR_OK;
+  }
+  if (X.given ? !B.p || !X.p : !B.p) return set_err(DHQR_EINVAL, X.given ? "null pointer argument" : "null b pointer");
+  if (B.stride < m) return set_err(DHQR_EINVAL, "strideb %lld < m=%lld", (long long)B.stride, (long long)m);
+  if (X.given && X.stride < n) return set_err(DHQR_EINVAL, "stridex %lld < n=%lld", (long long)X.stride, (long long)n);
+  return DHQR_OK;
+}
+#define CHECK_BATCHED(...)                       \
+  do {                                           \
+    bool empty_ = false;                         \
+    CHECK(check_batched(&empty_, __VA_ARGS__));  \
+    if (empty_) return DHQR_OK;                  \
+  } while (0)
+
+// ---- the wave tier: one wave per matrix, BQW_WAVES matrices per workgroup -------------------------------------------------
+static inline bool batched_wave_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
+  return c->small_route && c->batched_wave && m <= BQW_MAX_M && n <= BQW_MAX_N && n >= 1 && m >= n;
+}
+// the instantiation (columns held per wave) that serves n columns
+static inline int wave_nc(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : 32; }
+// one launch of kernel_<NC> for `batch_` matrices of n_ columns on c->stream (returns from the caller on a launch error)
+#define WAVE_LAUNCH(kernel_, n_, batch_, ...)                                                                   \
+  do {                                                                                                          \
+    const dim3 grid_((unsigned)(((batch_) + BQW_WAVES - 1) / BQW_WAVES)), block_(64 * BQW_WAVES);               \
+    switch (wave_nc(n_)) {                                                                                      \
+      case 8: hipLaunchKernelGGL((kernel_<8>), grid_, block_, 0, c->stream, __VA_ARGS__); break;                \
+      case 16: hipLaunchKernelGGL((kernel_<16>), grid_, block_, 0, c->stream, __VA_ARGS__); break;              \
+      default: hipLaunchKernelGGL((kernel_<32>), grid_, block_, 0, c->stream, __VA_ARGS__);                     \
+    }                                                                                                           \
+    LAUNCHCHECK();                                                                                              \
+  } while (0)
+// right-hand sides per group of the multi-column kernels (dhqr_batched_nrhs.h) in the instantiation NC
+template <typename T>
+static inline int wave_rg(int NC) {
+  if constexpr (std::is_same_v<T, double>) return BQN_RG_D(NC);
+  else return BQN_RG;
+}
+
+template <typename T>
+static int32_t wave_factor(dhqr_ctx *c, T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dalpha, int64_t stride_alpha,
+                           int64_t batch) {
+  CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
+  if constexpr (std::is_same_v<T, double>)
+    WAVE_LAUNCH(k_batched_qr_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+  else
+    WAVE_LAUNCH(k_batched_qr_wave_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+  if (c->profiling)  // (an element update reads and writes one T)
+    for (int64_t j = 0; j + 1 < n; ++j)
+      c->st.bytes_rank1 += (double)batch * (double)(2 * sizeof(T)) * (double)(m - j) * (double)(n - j - 1);
+  return prof_end(c);
+}
+template <typename T>
+static int32_t wave_solve(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *dalpha,
+                          int64_t stride_alpha, T *db, int64_t strideb, int64_t batch) {
+  CHECK(prof_begin(c, CAT_SOLVE));
+  if constexpr (std::is_same_v<T, double>)
+    WAVE_LAUNCH(k_batched_ldiv_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+  else
+    WAVE_LAUNCH(k_batched_ldiv_wave_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+  return prof_end(c);
+}
+// several right-hand sides per matrix: ONE launch of the multi-column kernels of dhqr_batched_nrhs.h
+template <typename T>
+static int32_t wave_solve_nrhs(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *dalpha,
+                               int64_t stride_alpha, T *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
+  CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
+  if constexpr (std::is_same_v<T, double>)
+    WAVE_LAUNCH(k_batched_ldiv_wave_nrhs, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  else
+    WAVE_LAUNCH(k_batched_ldiv_wave_nrhs_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  return prof_end(c);
+}
+// Does the multi-column kernel pay?  Measured (profiles/batched_nrhs_throughput.txt, batch 16384): the kernel is bound by
+// instruction issue, not by re-reading the matrix, and its time goes by GROUPS -- a group of rg chains costs 2.5 to 3.0
+// single-column solves whether its columns are real or the zeros of a tail.  nrhs = 2 loses everywhere (0.62 - 0.81 x the
+// column loop), nrhs = 4 in groups of three (Float64, n > 8) loses (0.77 - 0.80 x); nrhs = 4 in groups of four, 8 and 16 win
+// (1.01 - 1.23 x).  So: the kernel where the groups carry at least 2.6 real columns on average, the column loop -- the
+// same bits -- elsewhere.
+template <typename T>
+static inline bool nrhs_wave_pays(int64_t nrhs, int64_t n) {
+  const int rg = wave_rg<T>(wave_nc(n));
+  const int64_t groups = (nrhs + rg - 1) / rg;
+  return 5 * nrhs >= 13 * groups;
+}
+
+// ---- Float64 on the device ---------------------------------------------------------------------------------------------
+// (`single` belongs to the Float32 forms below; the Float64 single-matrix entry points are not in this file)
+static int32_t factor_batched(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
+                              int64_t stride_alpha, int64_t batch, int32_t nb, bool /*single*/ = false) {
+  const bool wave = batched_wave_fit(c, m, n);
+  const int fit = small_qr_fit(c, m, n);
+  if (!wave && fit < 0) {  // serial: one single-matrix factorisation after the other
+    // (and synchronised after each: the error word of the drivers' bounded waits belongs to one call at a time, dhqr.h)
+    for (int64_t k = 0; k < batch; ++k) {
+      CHECK(dhqr_factor_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, nb));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  c->tc_valid = false;  // whatever was kept for one of these matrices is gone
+  c->retry.valid = false;
+  if (wave) return wave_factor(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch);
+  CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
+  // the barrier form for every fit: with a batch in flight the compute units are full either way, and the barrier form
+  // has no bounded wait that could give up (same bits as the flag form)
+  const SmallBatch sb{batch, strideA, stride_alpha};
+  const int keep = c->small_flags;
+  c->small_flags = 0;
+  const int32_t rc = small_qr_launch_strided(c, fit, dA, lda, dA, lda, m, n, dalpha, nullptr, 0, sb);
+  c->small_flags = keep;
+  CHECK(rc);
+  if (c->profiling)
+    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 16.0 * (double)(m - j) * (double)(n - j - 1);
+  return prof_end(c);
+}
+
+static int32_t solve_batched(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *dalpha,
+                             int64_t stride_alpha, double *db, int64_t strideb, int64_t batch, bool /*single*/ = false) {
+  if (batched_wave_fit(c, m, n)) return wave_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch);
+  if (!small_ldiv_fit(c, m, n)) {
+    for (int64_t k = 0; k < batch; ++k) {  // (a solve's repetition, pipe_error_check, knows the last solve only)
+      CHECK(dhqr_solve_f64(c, dA + k * strideA, m, n, lda, dalpha + k * stride_alpha, db + k * strideb));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  CHECK(prof_begin(c, CAT_SOLVE));
+  const SmallBatch sb{batch, strideA, stride_alpha, strideb};
+  CHECK(small_ldiv_launch(c, dA, lda, m, n, dalpha, db, db, nullptr, nullptr, nullptr, 0, sb));  // (the factor is in HBM: no Awork)
+  return prof_end(c);
+}
+
+// The wave tier where it pays: the multi-column kernel.  Every other shape: the single-column route, column by column --
+// its tiers, its synchronisation, its profiling counts, its bits.
+static int32_t solve_batched_nrhs(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                  const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb, int64_t strideB,
+                                  int64_t batch) {
+  if (batched_wave_fit(c, m, n) && nrhs_wave_pays<double>(nrhs, n))
+    return wave_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+  for (int64_t r = 0; r < nrhs; ++r)
+    CHECK(solve_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
+  return DHQR_OK;
+}
+
+// ---- Float32 on the device: the native wave tier, else promoted ---------------------------------------------------------
+static int32_t f32_convert_launch(dhqr_ctx *c, bool widen, const void *src, int64_t lds, int64_t sstride, void *dst, int64_t ldd,
+                                  int64_t dstride, int64_t rows, int64_t cols, int64_t batch) {
+  const int64_t total = rows * cols * batch;
+  if (total <= 0) return DHQR_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
+  if (widen)
+    hipLaunchKernelGGL(k_widen_f32, dim3(grid), dim3(256), 0, c->stream, (const float *)src, lds, sstride, (double *)dst, ldd, dstride,
+                       rows, cols, batch);
+  else
+    hipLaunchKernelGGL(k_round_f32, dim3(grid), dim3(256), 0, c->stream, (const double *)src, lds, sstride, (float *)dst, ldd, dstride,
+                       rows, cols, batch);
+  LAUNCHCHECK();
+  return DHQR_OK;
+}
+
+static inline size_t f32_even(size_t n) { return (n + 1) & ~(size_t)1; }
+// The Float64 workspace of the promoted tier (c->f32_ws), packed: matrices (lda = m, matrix k at k m n) | alphas (n per
+// matrix) | right-hand sides (an m x nrhs block per matrix; nrhs = 0: none), each section starting on an even element
+// (16-byte boundaries, like separately allocated arrays).
+struct F32Ws {
+  double *A, *alpha, *B;
+};
+static int32_t f32_ws_get(dhqr_ctx *c, int64_t m, int64_t n, int64_t nrhs, int64_t batch, F32Ws &w) {
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  const size_t nB = (size_t)m * (size_t)nrhs * (size_t)batch;
+  CHECK(ensure(c, c->f32_ws, f32_even(na) + (nB ? f32_even(nal) + nB : nal)));
+  w.A = c->f32_ws.p;
+  w.alpha = w.A + f32_even(na);
+  w.B = w.alpha + f32_even(nal);
+  return DHQR_OK;
+}
+// The promoted tier: widen, call(w) -- the Float64 route on the workspace --, round back, synchronise where `sync` says.
+// dB == nullptr: a factorisation (A in; A and alpha out).  Else a solve (A, alpha and the m x nrhs blocks of B in; B out).
+template <typename Call>
+static int32_t f32_promoted(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
+                            int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, bool sync,
+                            Call call) {
+  F32Ws w;
+  CHECK(f32_ws_get(c, m, n, dB ? nrhs : 0, batch, w));
+  if (dB && c->tc_A == w.A) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
+  CHECK(f32_convert_launch(c, true, dA, lda, strideA, w.A, m, m * n, m, n, batch));
+  if (dB) {
+    CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, w.alpha, n, n, n, 1, batch));
+    CHECK(f32_convert_launch(c, true, dB, ldb, strideB, w.B, m, m * nrhs, m, nrhs, batch));
+  }
+  CHECK(call(w));
+  if (dB) {
+    CHECK(f32_convert_launch(c, false, w.B, m, m * nrhs, dB, ldb, strideB, m, nrhs, batch));
+  } else {  // (a factorisation's A and alpha are the caller's own, writable arrays)
+    CHECK(f32_convert_launch(c, false, w.A, m, m * n, const_cast<float *>(dA), lda, strideA, m, n, batch));
+    CHECK(f32_convert_launch(c, false, w.alpha, n, n, const_cast<float *>(dalpha), n, stride_alpha, n, 1, batch));
+  }
+  if (sync) HIPCHECK(hipStreamSynchronize(c->stream));
+  return DHQR_OK;
+}
+
+// `single`: the promoted tier calls dhqr_factor_f64 / dhqr_solve_f64 (else the batched routes above)
+static int32_t factor_batched(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
+                              int64_t stride_alpha, int64_t batch, int32_t nb, bool single) {
+  // (tc_valid / retry stay: what they remember are Float64 buffers, which a Float32 factorisation cannot overwrite -- the
+  // promoted tier's workspace goes through dhqr_factor_f64, which resets them itself)
+  if (batched_wave_fit(c, m, n)) return wave_factor(c, dA, m, n, lda, strideA, dalpha, stride_alpha, batch);
+  // synchronous where the Float64 route is: the blocked driver of a single matrix, the serial tier of a batch
+  const bool sync = small_qr_fit(c, m, n) < 0 && (!single || nb != 0);
+  return f32_promoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, nullptr, 0, 0, 0, batch, sync, [&](const F32Ws &w) {
+    return single ? dhqr_factor_f64(c, w.A, m, n, m, w.alpha, nb) : factor_batched(c, w.A, m, n, m, m * n, w.alpha, n, batch, nb);
+  });
+}
+
+static int32_t solve_batched(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
+                             int64_t stride_alpha, float *db, int64_t strideb, int64_t batch, bool single) {
+  if (batched_wave_fit(c, m, n)) return wave_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, strideb, batch);
+  const bool sync = !single && !small_ldiv_fit(c, m, n);  // (the serial tier of a batch)
+  return f32_promoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, db, 1, m, strideb, batch, sync, [&](const F32Ws &w) -> int32_t {
+    CHECK(single ? dhqr_solve_f64(c, w.A, m, n, m, w.alpha, w.B) : solve_batched(c, w.A, m, n, m, m * n, w.alpha, n, w.B, m, batch));
+    if (single && c->retry.valid && c->retry.b == w.B) {  // (a flag left by an earlier Float64 solve names another b)
+      // THIS solve took the persistent Q'b kernel and may be REPEATED by the next synchronising entry point (dhqr.h:
+      // dhqr_get_solve_retries) -- into the workspace, behind the rounding enqueued next.  Settle it first; afterwards nothing
+      // may come back to the remembered pointers: they lie in a workspace that a later call may reallocate.
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      const int32_t rc = pipe_error_check(c);
+      c->retry.valid = false;
+      CHECK(rc);
+    }
+    return DHQR_OK;
+  });
+}
+
+// The native multi-column kernel on the wave tier where it pays, the native single-column kernel column by column where
+// it does not; everything else PROMOTED once -- factor, alpha and all of B widened into the Float64 workspace, the Float64
+// route above, B rounded back.
+static int32_t solve_batched_nrhs(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
+                                  int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
+  if (batched_wave_fit(c, m, n)) {
+    if (nrhs_wave_pays<float>(nrhs, n))
+      return wave_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+    for (int64_t r = 0; r < nrhs; ++r)
+      CHECK(wave_solve(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
+    return DHQR_OK;
+  }
+  const bool sync = !small_ldiv_fit(c, m, n);  // (the serial tier)
+  return f32_promoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch, sync, [&](const F32Ws &w) {
+    return solve_batched_nrhs(c, w.A, m, n, m, m * n, w.alpha, n, w.B, nrhs, m, m * nrhs, batch);
+  });
+}
+
+// ---- the host forms ------------------------------------------------------------------------------------------------------
+// the packed device staging area of the host forms, `count` elements of T: matrices | alphas | right-hand sides
+template <typename T>
+static int32_t staging(dhqr_ctx *c, size_t count, T *&d) {
+  Buf &buf = std::is_same_v<T, double> ? c->batch_dev : c->f32_dev;
+  CHECK(ensure(c, buf, std::is_same_v<T, double> ? count : (count + 1) / 2));
+  d = reinterpret_cast<T *>(buf.p);
+  return DHQR_OK;
+}
+// host <-> device copies of `batch` blocks of rows x cols elements: block k at h + k hstride (leading dimension hld) and at
+// d + k dstride (leading dimension dld)
+template <typename T>
+static int32_t batch_copy(dhqr_ctx *c, T *d, int64_t dld, int64_t dstride, const T *h, int64_t hld, int64_t hstride, int64_t rows,
+                          int64_t cols, int64_t batch, bool up) {
+  auto copy2d = [&](T *dp, const T *hp, int64_t dpitch, int64_t hpitch, int64_t width, int64_t height) -> int32_t {
+    if (up)
+      HIPCHECK(hipMemcpy2DAsync(dp, dpitch * sizeof(T), hp, hpitch * sizeof(T), width * sizeof(T), height, hipMemcpyHostToDevice,
+                                c->stream));
+    else
+      HIPCHECK(hipMemcpy2DAsync(const_cast<T *>(hp), hpitch * sizeof(T), dp, dpitch * sizeof(T), width * sizeof(T), height,
+                                hipMemcpyDeviceToHost, c->stream));
+    return DHQR_OK;
+  };
+  // (for X the first path also takes nrhs = 1, and m = n with ldx = n, which the parent's two X paths -- the next two lines --
+  // sent through a column-pitch copy or the per-matrix loop: the same bytes in one copy)
+  if (cols == 1 || (hld == rows && dld == rows))  // every block contiguous
+    return copy2d(d, h, dstride, hstride, rows * cols, batch);
+  if ((hstride == hld * cols && dstride == dld * cols) || batch == 1)  // one column pitch throughout
+    return copy2d(d, h, dld, hld, rows, cols * batch);
+  for (int64_t k = 0; k < batch; ++k) CHECK(copy2d(d + k * dstride, h + k * hstride, dld, hld, rows, cols));
+  return DHQR_OK;
+}
+// the packed form of the staging area: leading dimension = rows, block k at k rows cols
+template <typename T>
+static int32_t batch_copy(dhqr_ctx *c, T *d, const T *h, int64_t rows, int64_t cols, int64_t hld, int64_t hstride, int64_t batch,
+                          bool up) {
+  return batch_copy(c, d, rows, rows * cols, h, hld, hstride, rows, cols, batch, up);
+}
+// what every host form ends with: the stream drained whatever happened (rc: the first error so far), then the bounded waits'
+// error word (a synchronous entry point reports it itself, after repeating a solve that has to be: dhqr.h)
+static int32_t host_finish(dhqr_ctx *c, int32_t rc, bool pipe_check) {
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DHQR_OK) rc = set_err(DHQR_EHIP, "hipStreamSynchronize failed");
+  if (pipe_check && rc == DHQR_OK) rc = pipe_error_check(c);
+  return rc;
+}
+
+template <typename T>
+static int32_t qr_host(dhqr_ctx *c, T *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *halpha, int64_t stride_alpha,
+                       int64_t batch, int32_t nb, bool single) {
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  T *dA;
+  CHECK(staging(c, na + nal, dA));
+  T *dal = dA + na;
+  int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
+  if (rc == DHQR_OK) rc = factor_batched(c, dA, m, n, m, m * n, dal, n, batch, nb, single);
+  if (rc == DHQR_OK) rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, false);
+  if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, false);
+  return host_finish(c, rc, true);
+}
+
+// nrhs columns per matrix: B_k at hB + k strideB (leading dimension ldb), X_k likewise.  `multi`: the _nrhs entry points,
+// through the multi-column solve; else nrhs = 1, ldb = m, ldx = n, through the single-column solve.
+constexpr bool SINGLE = true, BATCH = false;              // `single` of qr_host / ldiv_host / factor_batched / solve_batched
+constexpr bool MULTI_COLUMN = true, ONE_COLUMN = false;   // `multi` of ldiv_host
+template <typename T>
+static int32_t ldiv_host(dhqr_ctx *c, const T *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *halpha,
+                         int64_t stride_alpha, const T *hB, int64_t nrhs, int64_t ldb, int64_t strideB, T *hX, int64_t ldx,
+                         int64_t strideX, int64_t batch, bool single, bool multi) {
+  const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+  T *dA;
+  CHECK(staging(c, na + nal + (size_t)m * (size_t)nrhs * (size_t)batch, dA));
+  T *dal = dA + na, *dB = dal + nal;
+  int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
+  if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true);
+  if (rc == DHQR_OK) rc = batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true);  // src:318 copy of B
+  if (rc == DHQR_OK)
+    rc = multi ? solve_batched_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch)
+               : solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
+  if (rc == DHQR_OK) rc = host_finish(c, rc, true);  // (the serial tier's solves may have been repeated: dhqr.h)
+  if (rc == DHQR_OK)  // src:320: X_k = the first n rows of B_k
+    rc = batch_copy(c, dB, m, m * nrhs, hX, ldx, strideX, n, nrhs, batch, false);
+  return host_finish(c, rc, false);
+}

@@ -2,6 +2,8 @@
 // few host helpers that cross a unit boundary.  Units (csrc/build.sh compiles them side by side):
 //   dhqr_api.hip        context, blocked drivers (single GPU, column split, row split, one-process multi-GPU), solve,
 //                       ComplexF64, host I/O, every extern "C" entry point of include/dhqr.h
+//     dhqr_batched_host.h  (included by it, host code only) the small-matrix entry points' host side, once for double and
+//                       float: argument rules, wave-tier launch, promoted Float32 tier, staging, qr_host / ldiv_host
 //   dhqr_unblocked.hip  the nb = 0 path: dhqr_rank1.h's K-reflectors-per-pass kernels (84 % of the library's device code)
 //                       and their driver factor_unblocked_cols
 #pragma once
