@@ -102,6 +102,12 @@ SIGNATURES = {
     "dhqr_ldiv_batched_nrhs_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
     "dhqr_solve_batched_nrhs_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64]),
     "dhqr_ldiv_batched_nrhs_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_apply_q_batched_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i32]),
+    "dhqr_apply_q_batched_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i32]),
+    "dhqr_form_q_batched_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_form_q_batched_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_form_r_batched_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_form_r_batched_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64]),
     "dhqr_partialdot_f64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_partialdot_host_f64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_factor_c64": (_i32, [_p, _p, _i64, _i64, _i64, _p]),

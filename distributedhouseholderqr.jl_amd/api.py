@@ -710,38 +710,108 @@ def partialdot(a, b, lo: int, hi: int):
 
 
 # ------------------------------------------------------------------------------- metric helpers
-def apply_q_(H: DistributedHouseholderQRStruct, B, trans: bool):
-    """B <- Q' B (trans) or Q B, in place, device tensors only."""
-    ptr, m, n, lda, dev = _dev_matrix(H.A)
-    bptr, mb, nrhs, ldb, _ = _dev_matrix(B)
-    if mb != m:
-        raise ValueError("row mismatch")
-    ctx = get_context(dev)
+def _small_family(A) -> bool:
+    """does the factor belong to the entry points of the small-matrix family (dhqr_apply_q_batched_* ...): a (batch, m, n)
+    batch of either real type, or one float32 matrix (a batch of one)?  A 2-D float64 tensor keeps the blocked route."""
+    if not _is_tensor(A):
+        raise TypeError("device tensors only: the factor is a host array (apply_q_, get_q and get_r have no host form)")
+    if A.dtype not in (torch.float64, torch.float32):
+        raise TypeError("device path needs a float64 or float32 CUDA tensor")
+    return A.dim() == 3 or A.dtype == torch.float32
+
+
+def _colmajor_batch(A, what):
+    """(pointer, batch, rows, cols, ld, stride) of a device tensor of the small-matrix family: (batch, rows, cols) with
+    column-major matrices, or one column-major (rows, cols) matrix -- a batch of one.  Layouts are judged before residency
+    (_need_cuda), which needs no device."""
+    shape, strides = (tuple(A.shape), tuple(A.stride())) if A.dim() == 3 else ((1,) + tuple(A.shape), (0,) + tuple(A.stride()))
+    lay = _batch_layout(shape, strides) if len(shape) == 3 else None
+    if lay is None:
+        raise ValueError(f"{what}: column-major matrices required (unit stride down a column); build them with "
+                         "empty_colmajor or empty_colmajor_batched")
+    return (ctypes.c_void_p(A.data_ptr()),) + shape + lay
+
+
+def _need_cuda(*tensors):
+    if not all(x.is_cuda for x in tensors):
+        raise TypeError("device tensors only: the device path needs CUDA tensors")
+
+
+def _call_small_family(A, fn, *args):
+    ctx = get_context(A.device.index)
     ctx.use_torch_stream()
-    check(_lib.lib().dhqr_apply_q_f64(ctx.handle, ptr, m, n, lda, bptr, nrhs, ldb, 1 if trans else 0))
+    check(fn(ctx.handle, *args))
+    ctx.synchronize()
+
+
+def apply_q_(H: DistributedHouseholderQRStruct, B, trans: bool):
+    """B <- Q' B (trans) or Q B, in place, device tensors only.  One float64 matrix: the blocked route (dhqr_apply_q_f64).
+    A (batch, m, n) float64 or float32 batch with B (batch, m, nrhs), its matrices column-major like the factor's, and one
+    float32 matrix with B (m, nrhs): dhqr_apply_q_batched_f64 / _f32 -- one launch up to 64 x 32."""
+    _same_dtype(H.A, B, "B")
+    if not _small_family(H.A):
+        ptr, m, n, lda, dev = _dev_matrix(H.A)
+        bptr, mb, nrhs, ldb, _ = _dev_matrix(B)
+        if mb != m:
+            raise ValueError("row mismatch")
+        ctx = get_context(dev)
+        ctx.use_torch_stream()
+        check(_lib.lib().dhqr_apply_q_f64(ctx.handle, ptr, m, n, lda, bptr, nrhs, ldb, 1 if trans else 0))
+        return B
+    A = H.A
+    ptr, batch, m, n, lda, strideA = _colmajor_batch(A, "H.A")
+    if not _is_tensor(B) or B.dtype != A.dtype or B.dim() != A.dim() or tuple(B.shape[:-1]) != tuple(A.shape[:-2]) + (m,):
+        raise TypeError(f"B: {A.dtype} CUDA tensor of shape {tuple(A.shape[:-2]) + (m, 'nrhs')} expected")
+    bptr, _, _, nrhs, ldb, strideB = _colmajor_batch(B, "B")
+    _need_cuda(A, B)
+    L = _lib.lib()
+    fn = L.dhqr_apply_q_batched_f32 if _is_f32(A) else L.dhqr_apply_q_batched_f64
+    _call_small_family(A, fn, ptr, m, n, lda, strideA, bptr, nrhs, ldb, strideB, batch, 1 if trans else 0)
     return B
 
 
 def get_r(H: DistributedHouseholderQRStruct):
-    r"""n x n upper-triangular R of a Float64 device factorisation (strict upper part of H.A + α on the
-    diagonal, src:296-309), as a new column-major device tensor.  The reference exposes R only
+    r"""n x n upper-triangular R of a device factorisation (strict upper part of H.A + α on the
+    diagonal, src:296-309), as a new column-major device tensor; (batch, n, n) for a batch.  The reference exposes R only
     implicitly through `\`; SURVEY.md section 8f rank 2 asks for the explicit extraction."""
-    ptr, m, n, lda, dev = _dev_matrix(H.A)
-    W = empty_colmajor(m, n, H.A.device)
-    wptr, _, _, ldw, _ = _dev_matrix(W)
-    ctx = get_context(dev)
-    ctx.use_torch_stream()
-    check(_lib.lib().dhqr_form_r0_f64(ctx.handle, ptr, m, n, lda, _dev_vector(H.α, n), wptr, ldw, NB, 1, 0))
-    return W[:n, :]
+    _same_dtype(H.A, H.α, "α")
+    if not _small_family(H.A):
+        ptr, m, n, lda, dev = _dev_matrix(H.A)
+        W = empty_colmajor(m, n, H.A.device)
+        wptr, _, _, ldw, _ = _dev_matrix(W)
+        ctx = get_context(dev)
+        ctx.use_torch_stream()
+        check(_lib.lib().dhqr_form_r0_f64(ctx.handle, ptr, m, n, lda, _dev_vector(H.α, n), wptr, ldw, NB, 1, 0))
+        return W[:n, :]
+    A, α = H.A, H.α
+    ptr, batch, m, n, lda, strideA = _colmajor_batch(A, "H.A")
+    _need_cuda(A)
+    if not _is_tensor(α) or α.dtype != A.dtype or not α.is_cuda or tuple(α.shape) != tuple(A.shape[:-2]) + (n,) or not α.is_contiguous():
+        raise TypeError(f"α must be a contiguous {A.dtype} CUDA tensor of shape {tuple(A.shape[:-2]) + (n,)}")
+    R = empty_colmajor_batched(batch, n, n, A.device, A.dtype)
+    L = _lib.lib()
+    fn = L.dhqr_form_r_batched_f32 if _is_f32(A) else L.dhqr_form_r_batched_f64
+    _call_small_family(A, fn, ptr, m, n, lda, strideA, ctypes.c_void_p(α.data_ptr()), max(n, 1), ctypes.c_void_p(R.data_ptr()),
+                       max(n, 1), max(n * n, 1), batch)
+    return R if A.dim() == 3 else R[0]
 
 
 def get_q(H: DistributedHouseholderQRStruct):
-    """explicit thin Q (m x n, column-major device tensor): Q = H_1 ... H_n applied to [I; 0]."""
-    m, n = H.A.shape
-    Q = empty_colmajor(m, n, H.A.device)
-    Q.zero_()
-    Q.diagonal().fill_(1.0)
-    return apply_q_(H, Q, trans=False)
+    """explicit thin Q (m x n, column-major device tensor; (batch, m, n) for a batch): Q = H_1 ... H_n applied to [I; 0]."""
+    if not _small_family(H.A):
+        m, n = H.A.shape
+        Q = empty_colmajor(m, n, H.A.device)
+        Q.zero_()
+        Q.diagonal().fill_(1.0)
+        return apply_q_(H, Q, trans=False)
+    A = H.A
+    ptr, batch, m, n, lda, strideA = _colmajor_batch(A, "H.A")
+    _need_cuda(A)
+    Q = empty_colmajor_batched(batch, m, n, A.device, A.dtype)
+    L = _lib.lib()
+    fn = L.dhqr_form_q_batched_f32 if _is_f32(A) else L.dhqr_form_q_batched_f64
+    _call_small_family(A, fn, ptr, m, n, lda, strideA, ctypes.c_void_p(Q.data_ptr()), max(m, 1), max(m * n, 1), batch)
+    return Q if A.dim() == 3 else Q[0]
 
 
 def residual(H: DistributedHouseholderQRStruct, Aorig, work=None) -> float:

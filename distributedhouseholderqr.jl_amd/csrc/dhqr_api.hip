@@ -16,6 +16,7 @@
 #include "dhqr_batched.h"
 #include "dhqr_f32.h"
 #include "dhqr_batched_nrhs.h"
+#include "dhqr_batched_applyq.h"
 #include "dhqr_tsqr.h"
 
 static thread_local char g_err[512] = "";
@@ -1989,7 +1990,7 @@ int32_t dhqr_ldiv_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
 
 // ---- batches of small matrices, Float32, several right-hand sides per matrix (dhqr.h: dhqr_factor_batched_f64 ...) -------
 // The host side -- argument rules, tiers, staging -- is dhqr_batched_host.h, once for both element types; the kernels are
-// dhqr_batched.h, dhqr_f32.h, dhqr_batched_nrhs.h and dhqr_small.h.
+// dhqr_batched.h, dhqr_f32.h, dhqr_batched_nrhs.h, dhqr_batched_applyq.h and dhqr_small.h.
 int32_t dhqr_factor_batched_f64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
                                 int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);
@@ -2118,6 +2119,51 @@ int32_t dhqr_ldiv_batched_nrhs_f32(dhqr_ctx *c, const float *hA, int64_t m, int6
   CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB),
                 rhs_block(hX, nrhs, ldx, strideX));
   return ldiv_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hB, nrhs, ldb, strideB, hX, ldx, strideX, batch, BATCH, MULTI_COLUMN);
+}
+
+// Q application, explicit Q and R for batches and Float32 (dhqr.h: dhqr_apply_q_batched_f64 ...)
+int32_t dhqr_apply_q_batched_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dB,
+                                 int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dB, nrhs, ldb, strideB), "B", trans);
+  return apply_q_batched(c, dA, m, n, lda, strideA, dB, nrhs, ldb, strideB, batch, trans, APPLY_Q);
+}
+
+int32_t dhqr_apply_q_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dB,
+                                 int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dB, nrhs, ldb, strideB), "B", trans);
+  return apply_q_batched(c, dA, m, n, lda, strideA, dB, nrhs, ldb, strideB, batch, trans, APPLY_Q);
+}
+
+int32_t dhqr_form_q_batched_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dQ,
+                                int64_t ldq, int64_t strideQ, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dQ, n, ldq, strideQ), "Q", 0);
+  return apply_q_batched(c, dA, m, n, lda, strideA, dQ, n, ldq, strideQ, batch, 0, FORM_Q);
+}
+
+int32_t dhqr_form_q_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dQ,
+                                int64_t ldq, int64_t strideQ, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dQ, n, ldq, strideQ), "Q", 0);
+  return apply_q_batched(c, dA, m, n, lda, strideA, dQ, n, ldq, strideQ, batch, 0, FORM_Q);
+}
+
+int32_t dhqr_form_r_batched_f64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const double *dalpha, int64_t stride_alpha, double *dR, int64_t ldr, int64_t strideR, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_nrhs(dR, "R", n, n, ldr, strideR));
+  return form_r_batched(c, dA, n, lda, strideA, dalpha, stride_alpha, dR, ldr, strideR, batch);
+}
+
+int32_t dhqr_form_r_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const float *dalpha, int64_t stride_alpha, float *dR, int64_t ldr, int64_t strideR, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_nrhs(dR, "R", n, n, ldr, strideR));
+  return form_r_batched(c, dA, n, lda, strideA, dalpha, stride_alpha, dR, ldr, strideR, batch);
 }
 
 int32_t dhqr_partialdot_f64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,

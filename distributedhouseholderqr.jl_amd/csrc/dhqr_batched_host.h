@@ -1,5 +1,6 @@
 // dhqr_batched_host.h -- the host side of the small-matrix entry points (dhqr.h: dhqr_factor_batched_f64 ...
-// dhqr_ldiv_batched_nrhs_f32, and the Float32 single-matrix forms), written once for T = double and T = float.  Host code
+// dhqr_ldiv_batched_nrhs_f32, dhqr_apply_q_batched_f64 ... dhqr_form_r_batched_f32, and the Float32 single-matrix forms),
+// written once for T = double and T = float.  Host code
 // only; included by dhqr_api.hip ahead of its extern "C" block (templates need C++ linkage), which keeps the exported
 // functions themselves: ENTER, the argument check, one call into this file.
 // Tiers by shape.  Float64: one wave per matrix (dhqr_batched.h) | the single-workgroup kernels of dhqr_small.h with grid =
@@ -19,13 +20,14 @@ static int32_t check_nb(int32_t nb) {
   if (nb != 0 && nb != DHQR_NB) return set_err(DHQR_EINVAL, "nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_NB, nb);
   return DHQR_OK;
 }
+// (with_alpha = false: a call that takes the factor alone -- Q is made of the reflectors)
 static int32_t check_batch(const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
-                           int64_t stride_alpha, int64_t batch) {
+                           int64_t stride_alpha, int64_t batch, bool with_alpha = true) {
   CHECK(check_mat(A, m, n, lda, true));
-  if (!alpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  if (with_alpha && !alpha) return set_err(DHQR_EINVAL, "null alpha pointer");
   if (strideA < lda * (n - 1) + m)
     return set_err(DHQR_EINVAL, "strideA %lld < lda*(n-1)+m = %lld", (long long)strideA, (long long)(lda * (n - 1) + m));
-  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
+  if (with_alpha && stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
   if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
   return DHQR_OK;
 }
@@ -48,7 +50,7 @@ struct RhsArg {
 static inline RhsArg rhs_column(const void *p, int64_t rows, int64_t stride) { return RhsArg{p, 1, rows, stride, false, true}; }
 static inline RhsArg rhs_block(const void *p, int64_t nrhs, int64_t ld, int64_t stride) { return RhsArg{p, nrhs, ld, stride, true, true}; }
 // The preamble of every batched entry point.  What the call has beside A and alpha: nb (qr!) | B (a solve on the device) |
-// B and X (a solve on the host), both columns or both blocks.
+// B and X (a solve on the host), both columns or both blocks | nothing (form_r).
 // *empty: nothing to do (batch, n or nrhs is 0) -- and then no pointer, leading dimension or stride has been looked at.
 static int32_t check_batched(bool *empty, const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, const void *alpha,
                              int64_t stride_alpha, int64_t batch, const int32_t *nb, RhsArg B = RhsArg(), RhsArg X = RhsArg()) {
@@ -58,6 +60,7 @@ static int32_t check_batched(bool *empty, const void *A, int64_t m, int64_t n, i
   if (*empty) return DHQR_OK;
   CHECK(check_batch(A, m, n, lda, strideA, alpha, stride_alpha, batch));
   if (nb) return check_nb(*nb);
+  if (!B.given) return DHQR_OK;  // (the factor and alpha alone: form_r, which checks its R itself)
   if (B.block) {
     CHECK(check_nrhs(B.p, "B", m, B.nrhs, B.ld, B.stride));
     return X.given ? check_nrhs(X.p, "X", n, X.nrhs, X.ld, X.stride) : DHQR_OK;
@@ -73,6 +76,23 @@ static int32_t check_batched(bool *empty, const void *A, int64_t m, int64_t n, i
     CHECK(check_batched(&empty_, __VA_ARGS__));  \
     if (empty_) return DHQR_OK;                  \
   } while (0)
+// The preamble of the entry points that take a factor WITHOUT alpha and a block of m rows (apply_q: B; form_q: Q, nrhs = n).
+static int32_t check_batched_q(bool *empty, const void *A, int64_t m, int64_t n, int64_t lda, int64_t strideA, int64_t batch, RhsArg B,
+                               const char *name, int32_t trans) {
+  if (B.nrhs < 0) return set_err(DHQR_EINVAL, "negative nrhs %lld", (long long)B.nrhs);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (trans != 0 && trans != 1) return set_err(DHQR_EINVAL, "trans must be 0 (Q B) or 1 (Q'B); got %d", (int)trans);
+  *empty = B.nrhs == 0 || batch == 0 || no_columns(m, n);
+  if (*empty) return DHQR_OK;
+  CHECK(check_batch(A, m, n, lda, strideA, nullptr, 0, batch, false));
+  return check_nrhs(B.p, name, m, B.nrhs, B.ld, B.stride);
+}
+#define CHECK_BATCHED_Q(...)                       \
+  do {                                             \
+    bool empty_ = false;                           \
+    CHECK(check_batched_q(&empty_, __VA_ARGS__));  \
+    if (empty_) return DHQR_OK;                    \
+  } while (0)
 
 // ---- the wave tier: one wave per matrix, BQW_WAVES matrices per workgroup -------------------------------------------------
 static inline bool batched_wave_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
@@ -80,17 +100,20 @@ static inline bool batched_wave_fit(const dhqr_ctx *c, int64_t m, int64_t n) {
 }
 // the instantiation (columns held per wave) that serves n columns
 static inline int wave_nc(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : 32; }
-// one launch of kernel_<NC> for `batch_` matrices of n_ columns on c->stream (returns from the caller on a launch error)
-#define WAVE_LAUNCH(kernel_, n_, batch_, ...)                                                                   \
+// one launch of kernel_<NC targs_> for `batch_` matrices of n_ columns on c->stream (returns from the caller on a launch
+// error); targs_: nothing, or WAVE_TARGS(further template arguments)
+#define WAVE_TARGS(...) , __VA_ARGS__
+#define WAVE_LAUNCH_T(kernel_, targs_, n_, batch_, ...)                                                         \
   do {                                                                                                          \
     const dim3 grid_((unsigned)(((batch_) + BQW_WAVES - 1) / BQW_WAVES)), block_(64 * BQW_WAVES);               \
     switch (wave_nc(n_)) {                                                                                      \
-      case 8: hipLaunchKernelGGL((kernel_<8>), grid_, block_, 0, c->stream, __VA_ARGS__); break;                \
-      case 16: hipLaunchKernelGGL((kernel_<16>), grid_, block_, 0, c->stream, __VA_ARGS__); break;              \
-      default: hipLaunchKernelGGL((kernel_<32>), grid_, block_, 0, c->stream, __VA_ARGS__);                     \
+      case 8: hipLaunchKernelGGL((kernel_<8 targs_>), grid_, block_, 0, c->stream, __VA_ARGS__); break;         \
+      case 16: hipLaunchKernelGGL((kernel_<16 targs_>), grid_, block_, 0, c->stream, __VA_ARGS__); break;       \
+      default: hipLaunchKernelGGL((kernel_<32 targs_>), grid_, block_, 0, c->stream, __VA_ARGS__);              \
     }                                                                                                           \
     LAUNCHCHECK();                                                                                              \
   } while (0)
+#define WAVE_LAUNCH(kernel_, n_, batch_, ...) WAVE_LAUNCH_T(kernel_, , n_, batch_, __VA_ARGS__)
 // right-hand sides per group of the multi-column kernels (dhqr_batched_nrhs.h) in the instantiation NC
 template <typename T>
 static inline int wave_rg(int NC) {
@@ -130,6 +153,26 @@ static int32_t wave_solve_nrhs(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, i
     WAVE_LAUNCH(k_batched_ldiv_wave_nrhs, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
   else
     WAVE_LAUNCH(k_batched_ldiv_wave_nrhs_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  return prof_end(c);
+}
+// B_k <- Q_k'B_k | Q_k B_k | Q_k [I; 0]: ONE launch of the kernels of dhqr_batched_applyq.h
+constexpr bool FORM_Q = true, APPLY_Q = false;  // `formq` of wave_apply_q / apply_q_batched
+template <typename T>
+static int32_t wave_apply_q(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dB, int64_t nrhs, int64_t ldb,
+                            int64_t strideB, int64_t batch, int trans, bool formq) {
+  CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
+#define APPLYQ_LAUNCH(kernel_)                                                                                                 \
+  do {                                                                                                                         \
+    if (formq)                                                                                                                 \
+      WAVE_LAUNCH_T(kernel_, WAVE_TARGS(0, 1), n, batch, dA, lda, strideA, (int)m, (int)n, dB, (int)nrhs, ldb, strideB, batch); \
+    else if (trans)                                                                                                            \
+      WAVE_LAUNCH_T(kernel_, WAVE_TARGS(1), n, batch, dA, lda, strideA, (int)m, (int)n, dB, (int)nrhs, ldb, strideB, batch);    \
+    else                                                                                                                       \
+      WAVE_LAUNCH_T(kernel_, WAVE_TARGS(0), n, batch, dA, lda, strideA, (int)m, (int)n, dB, (int)nrhs, ldb, strideB, batch);    \
+  } while (0)
+  if constexpr (std::is_same_v<T, double>) APPLYQ_LAUNCH(k_batched_applyq_wave);
+  else APPLYQ_LAUNCH(k_batched_applyq_wave_s);
+#undef APPLYQ_LAUNCH
   return prof_end(c);
 }
 // Does the multi-column kernel pay?  Measured (profiles/batched_nrhs_throughput.txt, batch 16384): the kernel is bound by
@@ -239,18 +282,19 @@ static int32_t f32_ws_get(dhqr_ctx *c, int64_t m, int64_t n, int64_t nrhs, int64
   return DHQR_OK;
 }
 // The promoted tier: widen, call(w) -- the Float64 route on the workspace --, round back, synchronise where `sync` says.
-// dB == nullptr: a factorisation (A in; A and alpha out).  Else a solve (A, alpha and the m x nrhs blocks of B in; B out).
+// dB == nullptr: a factorisation (A in; A and alpha out).  Else a solve (A, alpha and the m x nrhs blocks of B in; B out);
+// dalpha == nullptr: an application of Q (no alpha: A and B in, B out); b_in = false: the explicit Q (A in, B out).
 template <typename Call>
 static int32_t f32_promoted(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *dalpha,
                             int64_t stride_alpha, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, bool sync,
-                            Call call) {
+                            Call call, bool b_in = true) {
   F32Ws w;
   CHECK(f32_ws_get(c, m, n, dB ? nrhs : 0, batch, w));
   if (dB && c->tc_A == w.A) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
   CHECK(f32_convert_launch(c, true, dA, lda, strideA, w.A, m, m * n, m, n, batch));
   if (dB) {
-    CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, w.alpha, n, n, n, 1, batch));
-    CHECK(f32_convert_launch(c, true, dB, ldb, strideB, w.B, m, m * nrhs, m, nrhs, batch));
+    if (dalpha) CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, w.alpha, n, n, n, 1, batch));
+    if (b_in) CHECK(f32_convert_launch(c, true, dB, ldb, strideB, w.B, m, m * nrhs, m, nrhs, batch));
   }
   CHECK(call(w));
   if (dB) {
@@ -311,6 +355,42 @@ static int32_t solve_batched_nrhs(dhqr_ctx *c, const float *dA, int64_t m, int64
   return f32_promoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch, sync, [&](const F32Ws &w) {
     return solve_batched_nrhs(c, w.A, m, n, m, m * n, w.alpha, n, w.B, nrhs, m, m * nrhs, batch);
   });
+}
+
+// ---- Q application, explicit Q and R (dhqr.h: dhqr_apply_q_batched_f64 ...) -----------------------------------------------
+// The wave tier: one launch.  Every other shape, Float64: matrix after matrix on apply_q_impl, the blocked route of
+// dhqr_apply_q_f64 (its bits) -- the explicit Q from [I; 0] --, all of it enqueued on the stream; Float32: PROMOTED.
+template <typename T>
+static int32_t apply_q_batched(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dB, int64_t nrhs,
+                               int64_t ldb, int64_t strideB, int64_t batch, int trans, bool formq) {
+  if (batched_wave_fit(c, m, n)) return wave_apply_q(c, dA, m, n, lda, strideA, dB, nrhs, ldb, strideB, batch, trans, formq);
+  if constexpr (std::is_same_v<T, double>) {
+    CHECK(check_mat(dB, m, nrhs, ldb, false));  // (the blocked route's limit on a leading dimension; dA: check_batch)
+    if (formq) {
+      const int64_t total = m * nrhs * batch;
+      hipLaunchKernelGGL(k_batched_eye, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dB,
+                         ldb, strideB, m, nrhs, batch);
+      LAUNCHCHECK();
+    }
+    for (int64_t k = 0; k < batch; ++k)
+      CHECK(apply_q_impl(c, dA + k * strideA, m, n, lda, nullptr, dB + k * strideB, nrhs, ldb, trans, false));
+    return DHQR_OK;
+  } else {
+    return f32_promoted(
+        c, dA, m, n, lda, strideA, nullptr, 0, dB, nrhs, ldb, strideB, batch, false,
+        [&](const F32Ws &w) { return apply_q_batched(c, w.A, m, n, m, m * n, w.B, nrhs, m, m * nrhs, batch, trans, formq); }, !formq);
+  }
+}
+
+// one element-wise launch for every shape and both element types (copies: nothing to promote)
+template <typename T>
+static int32_t form_r_batched(dhqr_ctx *c, const T *dA, int64_t n, int64_t lda, int64_t strideA, const T *dalpha, int64_t stride_alpha,
+                              T *dR, int64_t ldr, int64_t strideR, int64_t batch) {
+  const int64_t total = n * n * batch;
+  hipLaunchKernelGGL(k_batched_form_r<T>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dA,
+                     lda, strideA, n, dalpha, stride_alpha, dR, ldr, strideR, batch);
+  LAUNCHCHECK();
+  return DHQR_OK;
 }
 
 // ---- the host forms ------------------------------------------------------------------------------------------------------

@@ -336,6 +336,54 @@ int32_t dhqr_ldiv_batched_nrhs_f32(dhqr_ctx *ctx, const float *hA, int64_t m, in
                                    const float *halpha, int64_t stride_alpha, const float *hB, int64_t nrhs, int64_t ldb,
                                    int64_t strideB, float *hX, int64_t ldx, int64_t strideX, int64_t batch);
 
+/* ------------------------------------------------------------------ Q application, explicit Q and R: batches and Float32
+ * What dhqr_apply_q_f64 and dhqr_form_r0_f64 (below) do for one Float64 matrix, for every factorisation of the small-matrix
+ * family: k = 0 .. batch-1, Float64 and Float32; a single matrix is batch = 1.  Strided like the blocks above: H_k at
+ * dA + k*strideA (the factor dhqr_factor_batched_* left), B_k (m x nrhs, leading dimension ldb) at dB + k*strideB, Q_k (m x n,
+ * ldq) at dQ + k*strideQ, R_k (n x n, ldr) at dR + k*strideR.  All pointers are device-resident; every call is asynchronous
+ * on the context's stream.
+ *   dhqr_apply_q_batched_f64 / _f32  dB_k <- Q_k' dB_k (trans = 1) or Q_k dB_k (trans = 0), in place.  Q_k = H_0 ... H_{n-1} is
+ *                                    made of the reflectors alone: no alpha is taken.
+ *   dhqr_form_q_batched_f64 / _f32   dQ_k <- the explicit thin Q_k = Q_k [I; 0] (m x n).  dQ is written only: nothing of it
+ *                                    is read, all m rows of its n columns are written.
+ *   dhqr_form_r_batched_f64 / _f32   dR_k <- R_k: the strict upper part of H_k, alpha_k on the diagonal, zeros below
+ *                                    (src:296-309).  One element-wise launch for every shape and both types; copies only.
+ * Routes of apply_q and form_q, in this order:
+ *   m <= 64 and n <= 32      (small route on) ONE launch, one WAVE per matrix (csrc/dhqr_batched_applyq.h), whatever nrhs and
+ *                            batch: the factor is loaded into registers once, the columns walk past it in groups of up to four
+ *                            (three for Float64 with n > 16).  trans = 1 evaluates, per column, exactly the expressions of the
+ *                            Q'B phase of dhqr_solve_batched_nrhs_*: rows n .. m-1 of the result are BIT-IDENTICAL to the
+ *                            same rows of what that solve leaves in dB (the tail of Q'B).  trans = 0 applies the same
+ *                            expressions with the reflectors right to left.  form_q is trans = 0 on columns e_r made in
+ *                            registers, skipping the reflectors behind a group's last column (they act as the identity);
+ *                            for a finite factor it compares equal to trans = 0 applied to [I; 0].  Column r of a result
+ *                            depends neither on nrhs nor on its place nor on the batch.
+ *                            With profiling on: ONE n_solve group per call (the category of the solve whose first phase
+ *                            this is).  dhqr_form_r_batched_* is not counted.
+ *   every other shape, f64   a loop over the matrices on the blocked compact-WY route of dhqr_apply_q_f64: the bits of that
+ *                            call on matrix k alone, its profiling counts.  form_q: dQ_k <- [I; 0] by one small launch, then
+ *                            that loop with trans = 0.
+ *   every other shape, f32   PROMOTED: the factor and B are widened once into the Float64 workspace of the context
+ *                            (dhqr_trim), the Float64 entry point of this block runs on them (packed: leading dimension m),
+ *                            the result is rounded back: result = float32(f64 entry point(float64(input))) by definition.
+ * batch == 0, n == 0 or nrhs == 0: no-op, DHQR_OK, no pointer is looked at.  DHQR_EINVAL (nothing is written): batch < 0,
+ * nrhs < 0, m < n, a null pointer, lda < m, strideA < lda*(n-1) + m, ldb or ldq < m, ldr < n, a stride of B, Q or R shorter
+ * than its last column needs (ld*(cols-1) + rows), stride_alpha < n, trans outside {0, 1}. */
+int32_t dhqr_apply_q_batched_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dB,
+                                 int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans);
+int32_t dhqr_apply_q_batched_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dB,
+                                 int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans);
+int32_t dhqr_form_q_batched_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dQ,
+                                int64_t ldq, int64_t strideQ, int64_t batch);
+int32_t dhqr_form_q_batched_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dQ,
+                                int64_t ldq, int64_t strideQ, int64_t batch);
+int32_t dhqr_form_r_batched_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const double *dalpha, int64_t stride_alpha, double *dR, int64_t ldr, int64_t strideR,
+                                int64_t batch);
+int32_t dhqr_form_r_batched_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const float *dalpha, int64_t stride_alpha, float *dR, int64_t ldr, int64_t strideR,
+                                int64_t batch);
+
 /* KAT hook mirroring partialdot(a, b, lo:hi, Float64) (src:42-49; test/partialdot.jl:18):
  * sum_{i=lo}^{hi-1} da[i]*db[i] (0-based, hi exclusive) reduced on the device with the same
  * wavefront-shuffle + LDS tree the factor kernels use.  Synchronous (returns a host scalar). */
@@ -385,7 +433,8 @@ int32_t dhqr_partialdot_host_c64(dhqr_ctx *ctx, const double *ha, const double *
 /* ------------------------------------------------------------------ Q application / metric
  * dB (m x nrhs) <- Q' dB (trans = 1) or Q dB (trans = 0), Q = H_1 ... H_n from a factored dA.
  * Blocked compact-WY on MFMA (T is rebuilt per panel from V). No reference analogue beyond
- * src:215-242 (single vector); needed for the north-star metric ||A - QR|| / ||A||. Async. */
+ * src:215-242 (single vector); needed for the north-star metric ||A - QR|| / ||A||. Async.
+ * One Float64 matrix; batches and Float32: dhqr_apply_q_batched_f64 / _f32 above. */
 int32_t dhqr_apply_q_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda,
                          double *dB, int64_t nrhs, int64_t ldb, int32_t trans);
 

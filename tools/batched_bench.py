@@ -10,6 +10,13 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
                                                            dhqr_solve_batched_nrhs_* call against the loop of K
                                                            dhqr_solve_batched_* calls on the columns (the same resident factor;
                                                            the same bits, asserted); matrices/s and right-hand sides/s
+       --applyq {t,n,q} [--nrhs 16] [--batches 16384]      Q_k'B_k (t), Q_k B_k (n) or the explicit thin Q_k (q) of a resident
+                                                           batched factor: ONE dhqr_apply_q_batched_* / dhqr_form_q_batched_*
+                                                           call, against dhqr_solve_batched_nrhs_* at the same shape and nrhs
+                                                           (t does a strict subset of its work) and, Float64, against what a
+                                                           caller had before: a loop of dhqr_apply_q_f64, one call per matrix
+                                                           (on the first LOOP_BATCH matrices, scaled per matrix); ROUNDS
+                                                           rounds of 10 repetitions each, every round's median listed
 
 Per point: 3 warm-up and 10 timed repetitions of (restore the inputs, synchronise, START, calls, synchronise, STOP) on the
 host clock -- a caller's view, launch costs included; median and min-max of matrices per second; the ratio batched / looped
@@ -28,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(12, 6), (16, 8), (32, 16), (64, 32), (110, 100), (220, 200)]
 BATCHES = [64, 1024, 16384]
 WARMUP, REPS = 3, 10
+ROUNDS, LOOP_BATCH = 5, 256  # --applyq
 
 
 def point(m, n, batch, dtype="f64"):
@@ -143,6 +151,112 @@ def point_nrhs(m, n, batch, nrhs, dtype="f64"):
     print("POINT " + json.dumps(out), flush=True)
 
 
+def point_applyq(m, n, batch, nrhs, op, dtype="f64"):
+    """the factor stays resident; per repetition B is restored (t, n; q writes only), then ONE call"""
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as g
+    pkg = g.import_package()
+    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    os.environ["DHQR_SMALL"] = "1"
+    cols = n if op == "q" else nrhs
+    A = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
+    B0 = pkg.empty_colmajor_batched(batch, m, cols, "cuda:0", dtype=tdt)
+    if op == "q":
+        B0.zero_()
+        B0.diagonal(dim1=1, dim2=2).fill_(1.0)  # [I; 0]: what the loop of single calls starts from
+    else:
+        for r in range(cols):
+            B0[:, :, r] = pkg.rand_colmajor_batched(batch, m, 1, 7 + 1000 * r, "cuda:0", dtype=tdt).reshape(batch, m)
+    B = B0.clone(memory_format=torch.preserve_format)
+    assert B.stride() == B0.stride() == (m * cols, 1, m)
+    H = pkg.qr_batched_(A)
+    torch.cuda.synchronize()
+    L = pkg._lib.lib()
+    P = ctypes.c_void_p
+    pa, pal, pb = A.data_ptr(), H.α.data_ptr(), B.data_ptr()
+    apply_b, form_q, solve_n = (getattr(L, f"dhqr_{k}_{dtype}") for k in ("apply_q_batched", "form_q_batched", "solve_batched_nrhs"))
+    trans = 1 if op == "t" else 0
+
+    def measure(ctx, fn, count):
+        rates = []
+        for r in range(WARMUP + REPS):
+            B.copy_(B0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(ctx.handle)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(count / dt)
+        return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
+
+    def new(h):
+        if op == "q":
+            pkg._lib.check(form_q(h, P(pa), m, n, m, m * n, P(pb), m, m * cols, batch))
+        else:
+            pkg._lib.check(apply_b(h, P(pa), m, n, m, m * n, P(pb), cols, m, m * cols, batch, trans))
+
+    def solve(h):
+        pkg._lib.check(solve_n(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), cols, m, m * cols, batch))
+
+    lb = min(batch, LOOP_BATCH)
+
+    def looped(h):
+        for k in range(lb):
+            pkg._lib.check(L.dhqr_apply_q_f64(h, P(pa + esz * k * m * n), m, n, m, P(pb + esz * k * m * cols), cols, m, trans))
+
+    out = {"m": m, "n": n, "batch": batch, "nrhs": cols, "op": op, "dtype": dtype, "loop_batch": lb, "new": [], "solve": [], "looped": []}
+    ctx = pkg.Context(0)
+    for _ in range(ROUNDS):
+        out["new"].append(measure(ctx, new, batch))
+        out["solve"].append(measure(ctx, solve, batch))
+        if dtype == "f64":
+            out["looped"].append(measure(ctx, looped, lb))
+    ctx.close()
+    print("POINT " + json.dumps(out), flush=True)
+
+
+def main_applyq(a, shapes, batches):
+    t, K, op = a.dtype, (a.nrhs or 16), a.applyq
+    what = {"t": "B_k <- Q_k'B_k", "n": "B_k <- Q_k B_k", "q": "explicit thin Q_k (nrhs = n)"}[op]
+    call = f"dhqr_form_q_batched_{t}" if op == "q" else f"dhqr_apply_q_batched_{t} (trans = {1 if op == 't' else 0})"
+    lines = [f"# tools/batched_bench.py --applyq {op} --nrhs {K} --dtype {t}: {what}, resident factor; matrices per second",
+             f"# {ROUNDS} rounds of {REPS} timed repetitions in one process: every round's median, then min .. max over all repetitions",
+             f"# new = one {call}; solve = one dhqr_solve_batched_nrhs_{t}, same shape and columns; looped (Float64) = "
+             f"dhqr_apply_q_f64 per matrix on the first {LOOP_BATCH} matrices, per matrix"]
+    print("\n".join(lines), flush=True)
+
+    def rounds(rs):
+        return (" ".join(f"{r['median']:.0f}" for r in rs) + f" ({min(r['min'] for r in rs):.0f} .. {max(r['max'] for r in rs):.0f})")
+
+    rc = 0
+    for (m, n) in shapes:
+        for batch in batches:
+            p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
+                                str(m), str(n), str(batch), "--dtype", t, "--nrhs", str(K), "--applyq", op], capture_output=True, text=True)
+            row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
+            if p.returncode != 0 or not row:
+                lines.append(f"{m}x{n} batch {batch} applyq {op}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
+                print(lines[-1], flush=True)
+                rc = 1
+                break
+            r = json.loads(row[0][6:])
+            med = lambda rs: statistics.median(x["median"] for x in rs)
+            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} nrhs {r['nrhs']:3d} {t} {op} | new {rounds(r['new'])} | solve {rounds(r['solve'])} | "
+                   f"new/solve {med(r['new']) / med(r['solve']):5.2f}x")
+            if r["looped"]:
+                txt += f" | looped {rounds(r['looped'])} | new/looped {med(r['new']) / med(r['looped']):8.0f}x"
+            lines.append(txt)
+            print(txt, flush=True)
+        if rc:
+            break
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return rc
+
+
 def fmt(r):
     return f"{r['median']:12.0f} ({r['min']:.0f} .. {r['max']:.0f})"
 
@@ -183,11 +297,14 @@ def main():
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64")
     ap.add_argument("--shapes", default=None, help="e.g. 16x8,32x16 (default: every shape)")
     ap.add_argument("--nrhs", type=int, default=None, help="right-hand sides per matrix: the multi-column solve against the column loop")
+    ap.add_argument("--applyq", choices=("t", "n", "q"), default=None, help="Q'B, QB or the explicit Q of a resident batched factor")
     ap.add_argument("--batches", default=None, help="e.g. 16384 or 64,1024 (default: every batch of BATCHES)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
     a = ap.parse_args()
     if a.point:
-        if a.nrhs is not None:
+        if a.applyq is not None:
+            point_applyq(*a.point, a.nrhs or 16, a.applyq, a.dtype)
+        elif a.nrhs is not None:
             point_nrhs(*a.point, a.nrhs, a.dtype)
         else:
             point(*a.point, a.dtype)
@@ -195,6 +312,8 @@ def main():
     t = a.dtype
     shapes = SHAPES if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
     batches = BATCHES if a.batches is None else [int(v) for v in a.batches.split(",")]
+    if a.applyq is not None:
+        return main_applyq(a, shapes, batches if a.batches is not None else [16384])
     if a.nrhs is not None:
         return main_nrhs(a, shapes, batches)
     lines = ["# tools/batched_bench.py: qr! + \\ of `batch` matrices, matrices per second, median (min .. max) of 10 repetitions",
