@@ -116,6 +116,10 @@ SIGNATURES = {
     "dhqr_qr_c64_nb": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i32]),
     "dhqr_solve_c64": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "dhqr_ldiv_c64": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "dhqr_factor_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i32]),
+    "dhqr_solve_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_qr_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i32]),
+    "dhqr_ldiv_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64]),
     "dhqr_partialdot_c64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_partialdot_host_c64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_apply_q_f64": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32]),

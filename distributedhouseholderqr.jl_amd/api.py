@@ -153,6 +153,14 @@ def _same_dtype(A, v, name):
         raise TypeError(f"{name} is {dt} but the matrix is {A.dtype}: convert one of them explicitly")
 
 
+def _same_field(A, v, name):
+    """the ComplexF64 methods are separate from the real ones: a real vector with a complex matrix, or the reverse, is a
+    TypeError, never a silent conversion (of a real b) or a dropped imaginary part (of a complex one)"""
+    dt = getattr(v, "dtype", None)
+    if dt is not None and _is_complex(A) != (dt == np.complex128 or (torch is not None and dt == torch.complex128)):
+        raise TypeError(f"{name} is {dt} but the matrix is {A.dtype}: convert one of them explicitly")
+
+
 def _resolve_dtype(dtype):
     """torch dtype of a `dtype` argument (None = float64, today's behaviour); float32 and float64 in torch's or numpy's spelling"""
     if dtype is None or dtype in (torch.float64, np.float64, "float64"):
@@ -182,10 +190,10 @@ def _resolve_nb(A, nb):
         if nb not in (None, 0, _lib.ZNB):
             raise ValueError(f"ComplexF64: nb must be None, 0 (unblocked) or {_lib.ZNB} (blocked)")
         if nb is None:
-            return _lib.ZNB if A.shape[1] >= 256 else 0
+            return _lib.ZNB if A.shape[-1] >= 256 else 0  # (a batch (batch, m, n): the shape of its matrices)
         return nb
     if nb is None:
-        return 0 if A.shape[0] <= DEFAULT_UNBLOCKED_MAX_ROWS else NB
+        return 0 if A.shape[-2] <= DEFAULT_UNBLOCKED_MAX_ROWS else NB
     return nb
 
 
@@ -514,6 +522,23 @@ def rand_colmajor_batched(batch: int, m: int, n: int, seed: int, device="cuda", 
     return A
 
 
+def empty_colmajor_batched_c(batch: int, m: int, n: int, device="cuda"):
+    """uninitialised (batch, m, n) complex128 device tensor whose matrices are column-major (stride(1) == 1, lda = m)."""
+    return torch.empty((batch, n, m), dtype=torch.complex128, device=device).transpose(1, 2)
+
+
+def rand_colmajor_batched_c(batch: int, m: int, n: int, seed: int, device="cuda"):
+    """matrix k = rand_colmajor_c(m, n, seed + k): the shared generator over the interleaved real view, so the oracle's
+    rand_matrix_c(m, n, seed + k) is its twin."""
+    A = empty_colmajor_batched_c(batch, m, n, device)
+    ctx = get_context(A.device.index)
+    ctx.use_torch_stream()
+    L = _lib.lib()
+    for k in range(batch):
+        check(L.dhqr_fill_uniform_f64(ctx.handle, ctypes.c_void_p(A[k].data_ptr()), 2 * m, n, 2 * m, seed + k, 2 * m, 0, NB, 1, 0))
+    return A
+
+
 def _batch_layout(shape, strides):
     """(lda, strideA) in elements of a (batch, m, n) array whose matrices are column-major, else None"""
     batch, m, n = shape
@@ -542,18 +567,24 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
     """qr!(A[k]) for every matrix of a (batch, m, n) float64 batch in ONE call (dhqr_factor_batched_f64 /
     dhqr_qr_batched_f64): one wave per matrix up to 64 x 32, one workgroup per matrix up to the small route's shapes, a
     serial loop beyond.  A is a CUDA tensor whose matrices are column-major (empty_colmajor_batched) or a numpy array; a
-    host array in another layout is copied to that layout and back.  Mutates A; returns the struct with α of shape (batch, n)."""
+    host array in another layout is copied to that layout and back.  Mutates A; returns the struct with α of shape (batch, n).
+    float32: dhqr_*_batched_f32.  complex128 (empty_colmajor_batched_c): dhqr_factor_batched_c64 / dhqr_qr_batched_c64 -- one
+    wave per matrix up to 64 x 32, a serial loop of single factorisations beyond; nb is None, 0 or ZNB (_resolve_nb)."""
     L = _lib.lib()
     if A.ndim != 3:
         raise ValueError("(batch, m, n) array expected")
     batch, m, n = A.shape
-    if nb is None:
+    cplx = _is_complex(A)
+    if cplx:
+        nb = _resolve_nb(A, nb)
+    elif nb is None:
         nb = 0 if m <= DEFAULT_UNBLOCKED_MAX_ROWS else NB
     f32 = _is_f32(A)
-    factor, qr = (L.dhqr_factor_batched_f32, L.dhqr_qr_batched_f32) if f32 else (L.dhqr_factor_batched_f64, L.dhqr_qr_batched_f64)
+    factor, qr = ((L.dhqr_factor_batched_c64, L.dhqr_qr_batched_c64) if cplx else
+                  (L.dhqr_factor_batched_f32, L.dhqr_qr_batched_f32) if f32 else (L.dhqr_factor_batched_f64, L.dhqr_qr_batched_f64))
     if _is_tensor(A):
-        if A.dtype not in (torch.float64, torch.float32) or not A.is_cuda:
-            raise TypeError("device path needs a float64 or float32 CUDA tensor")
+        if A.dtype not in (torch.float64, torch.float32, torch.complex128) or not A.is_cuda:
+            raise TypeError("device path needs a float64, float32 or complex128 CUDA tensor")
         lay = _batch_layout(A.shape, A.stride())
         if lay is None:
             raise ValueError("matrices of the batch must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
@@ -564,8 +595,8 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
                                         ctypes.c_void_p(H.α.data_ptr()), max(n, 1), batch, nb))
         ctx.synchronize()
         return H
-    if not isinstance(A, np.ndarray) or A.dtype not in (np.float64, np.float32):
-        raise TypeError("float64 or float32 numpy array or CUDA tensor expected")
+    if not isinstance(A, np.ndarray) or A.dtype not in (np.float64, np.float32, np.complex128):
+        raise TypeError("float64, float32 or complex128 numpy array or CUDA tensor expected")
     F, lda, strideA = _host_batch(A)
     H = DistributedHouseholderQRStruct(A)
     check(qr(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lda, strideA,
@@ -635,18 +666,25 @@ def _ldiv_batched_nrhs(H: DistributedHouseholderQRStruct, B):
 
 def ldiv_batched(H: DistributedHouseholderQRStruct, b):
     """`H[k] \\ b[k]` for every matrix of a batched factorisation: b (batch, m) -> x (batch, n); b is NOT modified.
-    b (batch, m, nrhs), its matrices column-major like A's: every column of every b[k] -> X (batch, n, nrhs)."""
+    b (batch, m, nrhs), its matrices column-major like A's: every column of every b[k] -> X (batch, n, nrhs); real factors
+    only -- a complex128 factor takes b (batch, m) complex128 (dhqr_solve_batched_c64 / dhqr_ldiv_batched_c64)."""
     L = _lib.lib()
     A, α = H.A, H.α
     if A.ndim != 3:
         raise ValueError("batched factorisation expected")
     batch, m, n = A.shape
     f32 = _is_f32(A)
+    cplx = _is_complex(A)
     _same_dtype(A, α, "α")
     _same_dtype(A, b, "b")
+    _same_field(A, α, "α")
+    _same_field(A, b, "b")
     if getattr(b, "ndim", 2) == 3:
+        if cplx:
+            raise TypeError("ComplexF64: vector right-hand side only")
         return _ldiv_batched_nrhs(H, b)
-    solve, ldiv_ = (L.dhqr_solve_batched_f32, L.dhqr_ldiv_batched_f32) if f32 else (L.dhqr_solve_batched_f64, L.dhqr_ldiv_batched_f64)
+    solve, ldiv_ = ((L.dhqr_solve_batched_c64, L.dhqr_ldiv_batched_c64) if cplx else
+                    (L.dhqr_solve_batched_f32, L.dhqr_ldiv_batched_f32) if f32 else (L.dhqr_solve_batched_f64, L.dhqr_ldiv_batched_f64))
     if _is_tensor(A):
         lay = _batch_layout(A.shape, A.stride())
         if lay is None:

@@ -14,6 +14,7 @@
 #include "dhqr_qtb.h"
 #include "dhqr_small.h"
 #include "dhqr_batched.h"
+#include "dhqr_batched_complex.h"
 #include "dhqr_f32.h"
 #include "dhqr_batched_nrhs.h"
 #include "dhqr_batched_applyq.h"
@@ -2490,6 +2491,57 @@ int32_t dhqr_ldiv_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
   (void)hipFree(dal);
   (void)hipFree(db);
   return rc;
+}
+
+// ---- batches of small ComplexF64 matrices (dhqr.h: dhqr_factor_batched_c64 ...) ------------------------------------------
+// The argument rules are those of the Float64 batched family (check_batched), in complex elements; nb: 0 or DHQR_ZNB; device
+// pointers are 16-byte aligned.  Tiers and host forms: dhqr_batched_host.h; kernels: dhqr_batched_complex.h.
+static int32_t check_znb(int32_t nb) {
+  if (nb != 0 && nb != DHQR_ZNB)
+    return set_err(DHQR_EINVAL, "ComplexF64: nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_ZNB, nb);
+  return DHQR_OK;
+}
+
+int32_t dhqr_factor_batched_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
+                                int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_znb(nb));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  return factor_batched(c, reinterpret_cast<double2 *>(dA), m, n, lda, strideA, reinterpret_cast<double2 *>(dalpha), stride_alpha, batch,
+                        nb);
+}
+
+int32_t dhqr_solve_batched_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const double *dalpha, int64_t stride_alpha, double *db, int64_t strideb, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_column(db, m, strideb));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  CHECK(check_zptr(db, "b"));
+  return solve_batched(c, reinterpret_cast<const double2 *>(dA), m, n, lda, strideA, reinterpret_cast<const double2 *>(dalpha),
+                       stride_alpha, reinterpret_cast<double2 *>(db), strideb, batch);
+}
+
+int32_t dhqr_qr_batched_c64(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
+                            int64_t stride_alpha, int64_t batch, int32_t nb) {
+  ENTER(c);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr);
+  CHECK(check_znb(nb));
+  return qr_host(c, reinterpret_cast<double2 *>(hA), m, n, lda, strideA, reinterpret_cast<double2 *>(halpha), stride_alpha, batch, nb,
+                 BATCH);
+}
+
+int32_t dhqr_ldiv_batched_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
+                              int64_t stridex, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_column(hb, m, strideb),
+                rhs_column(hx, n, stridex));
+  return ldiv_host(c, reinterpret_cast<const double2 *>(hA), m, n, lda, strideA, reinterpret_cast<const double2 *>(halpha),
+                   stride_alpha, reinterpret_cast<const double2 *>(hb), 1, m, strideb, reinterpret_cast<double2 *>(hx), n, stridex,
+                   batch, BATCH, ONE_COLUMN);
 }
 
 int32_t dhqr_partialdot_c64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,

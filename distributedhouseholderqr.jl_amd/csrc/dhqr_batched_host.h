@@ -7,6 +7,9 @@
 // batch, in their barrier form | a host loop over the single-matrix drivers.  Float32: m <= 64 and n <= 32 with the small
 // route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single matrix is a batch of 1) --, everything else
 // PROMOTED: widened into a Float64 workspace of the context, the Float64 route with the caller's nb, rounded back.
+// ComplexF64 (dhqr_factor_batched_c64 ... dhqr_ldiv_batched_c64): the wave tier -- one launch of the kernels of
+// dhqr_batched_complex.h -- | a host loop over dhqr_factor_c64_nb / dhqr_solve_c64; the host forms are those of the real types
+// with T = double2.
 // The host forms (qr_host, ldiv_host) end alike: after a failure of any step they still reach the final
 // hipStreamSynchronize -- nothing is left in flight on the caller's arrays -- and return the FIRST error.  (Before, the
 // single-column ldiv forms returned from a failed enqueue of the copy of X without it.)
@@ -393,12 +396,49 @@ static int32_t form_r_batched(dhqr_ctx *c, const T *dA, int64_t n, int64_t lda, 
   return DHQR_OK;
 }
 
+// ---- ComplexF64 on the device: the wave tier, else matrix after matrix ---------------------------------------------------
+// (lda and the strides count complex elements; nb was checked by the caller: 0 or DHQR_ZNB, ignored on the wave tier)
+static int32_t factor_batched(dhqr_ctx *c, double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double2 *dalpha,
+                              int64_t stride_alpha, int64_t batch, int32_t nb, bool /*single*/ = false) {
+  if (!batched_wave_fit(c, m, n)) {  // serial: that call's bits and profiling counts, synchronised after each (see Float64)
+    for (int64_t k = 0; k < batch; ++k) {
+      CHECK(dhqr_factor_c64_nb(c, reinterpret_cast<double *>(dA + k * strideA), m, n, lda,
+                               reinterpret_cast<double *>(dalpha + k * stride_alpha), nb));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  // (tc_valid / retry stay, as in dhqr_factor_c64: what they remember are Float64 factors and solves)
+  CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
+  WAVE_LAUNCH(k_batched_zqr_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+  if (c->profiling)  // (an element update reads and writes one complex element)
+    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 32.0 * (double)(m - j) * (double)(n - j - 1);
+  return prof_end(c);
+}
+
+static int32_t solve_batched(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double2 *dalpha,
+                             int64_t stride_alpha, double2 *db, int64_t strideb, int64_t batch, bool /*single*/ = false) {
+  if (!batched_wave_fit(c, m, n)) {
+    for (int64_t k = 0; k < batch; ++k) {
+      CHECK(dhqr_solve_c64(c, reinterpret_cast<const double *>(dA + k * strideA), m, n, lda,
+                           reinterpret_cast<const double *>(dalpha + k * stride_alpha), reinterpret_cast<double *>(db + k * strideb)));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      CHECK(pipe_error_check(c));
+    }
+    return DHQR_OK;
+  }
+  CHECK(prof_begin(c, CAT_SOLVE));
+  WAVE_LAUNCH(k_batched_zldiv_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+  return prof_end(c);
+}
+
 // ---- the host forms ------------------------------------------------------------------------------------------------------
 // the packed device staging area of the host forms, `count` elements of T: matrices | alphas | right-hand sides
 template <typename T>
 static int32_t staging(dhqr_ctx *c, size_t count, T *&d) {
-  Buf &buf = std::is_same_v<T, double> ? c->batch_dev : c->f32_dev;
-  CHECK(ensure(c, buf, std::is_same_v<T, double> ? count : (count + 1) / 2));
+  Buf &buf = std::is_same_v<T, float> ? c->f32_dev : c->batch_dev;  // (both buffers count doubles; double2: batch_dev)
+  CHECK(ensure(c, buf, (count * sizeof(T) + sizeof(double) - 1) / sizeof(double)));
   d = reinterpret_cast<T *>(buf.p);
   return DHQR_OK;
 }
@@ -468,9 +508,13 @@ static int32_t ldiv_host(dhqr_ctx *c, const T *hA, int64_t m, int64_t n, int64_t
   int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
   if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true);
   if (rc == DHQR_OK) rc = batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true);  // src:318 copy of B
-  if (rc == DHQR_OK)
-    rc = multi ? solve_batched_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch)
-               : solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
+  if (rc == DHQR_OK) {
+    if constexpr (std::is_same_v<T, double2>)  // (ComplexF64 has the single-column solve only)
+      rc = solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
+    else
+      rc = multi ? solve_batched_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch)
+                 : solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
+  }
   if (rc == DHQR_OK) rc = host_finish(c, rc, true);  // (the serial tier's solves may have been repeated: dhqr.h)
   if (rc == DHQR_OK)  // src:320: X_k = the first n rows of B_k
     rc = batch_copy(c, dB, m, m * nrhs, hX, ldx, strideX, n, nrhs, batch, false);

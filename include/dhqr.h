@@ -38,7 +38,8 @@ extern "C" {
                           * dhqr_factor_f32, dhqr_solve_f32, dhqr_qr_f32, dhqr_ldiv_f32, dhqr_factor_batched_f32, dhqr_solve_batched_f32,
                           * dhqr_qr_batched_f32, dhqr_ldiv_batched_f32;
                           * dhqr_solve_batched_nrhs_f64, dhqr_ldiv_batched_nrhs_f64, dhqr_solve_batched_nrhs_f32,
-                          * dhqr_ldiv_batched_nrhs_f32 */
+                          * dhqr_ldiv_batched_nrhs_f32;
+                          * dhqr_factor_batched_c64, dhqr_solve_batched_c64, dhqr_qr_batched_c64, dhqr_ldiv_batched_c64 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -429,6 +430,40 @@ int32_t dhqr_partialdot_c64(dhqr_ctx *ctx, const double *da, const double *db, i
                             double *hout);
 int32_t dhqr_partialdot_host_c64(dhqr_ctx *ctx, const double *ha, const double *hb, int64_t lo,
                                  int64_t hi, double *hout);
+
+/* ------------------------------------------------------------------ batches of small ComplexF64 matrices
+ * The ComplexF64 counterparts of the four batched Float64 entry points (dhqr_factor_batched_f64 ...): `qr!(A_k)` and
+ * `qr!(A_k) \ b_k` for k = 0 .. batch-1, every matrix with its own factor and its own single right-hand side.  The same
+ * arguments and the same strided layout, with the conventions of the ComplexF64 section: pointers are interleaved (re, im)
+ * doubles, lda and EVERY stride count complex elements, device pointers are 16-byte aligned.  nb is 0 or DHQR_ZNB.  The
+ * factor format of every matrix is the single-matrix one (alpha_k complex: n complex elements per matrix).
+ * Routes by shape, in this order:
+ *   m <= 64 and n <= 32      (small route on) ONE launch, one WAVE per matrix and four matrices per workgroup
+ *                            (csrc/dhqr_batched_complex.h): the reference's column-by-column algorithm with row l of the
+ *                            matrix, as (re, im), in lane l; column norms in double-double, alphafactor(0) = -1 (src:9); the
+ *                            solve carries both parts of b in double-double and divides by alpha_j as dhqr_solve_c64 does.
+ *                            Asynchronous on the ctx stream.  nb is ignored.  With profiling on a factor counts ONE n_rank1
+ *                            group and a solve one n_solve, whatever the batch.
+ *   everything else, and every shape when the small route is off (dhqr_set_small_route(ctx, 0), DHQR_SMALL=0)
+ *                            a host loop over dhqr_factor_c64_nb (with the caller's nb) / dhqr_solve_c64 on matrix k alone:
+ *                            serial, synchronised after every matrix; that call's bits and its profiling counts.
+ *                            Synchronous.  (A one-workgroup tier like the Float64 one does not exist for ComplexF64.)
+ *   dhqr_qr_batched_c64, dhqr_ldiv_batched_c64
+ *                            host in / host out, synchronous; staged through the context's device copy of a batch (the one
+ *                            dhqr_qr_batched_f64 uses; dhqr_trim releases it).  On an error return hA is undefined; hb is not
+ *                            modified (src:318).
+ * batch == 0 or n == 0: no-op that looks at no pointer, DHQR_OK.  DHQR_EINVAL, and nothing is written: batch < 0, m < n,
+ * lda < m, strideA < lda*(n-1) + m, stride_alpha < n, strideb < m, stridex < n, null pointers, another nb, a device pointer
+ * that is not 16-byte aligned.  Several right-hand sides per matrix, Q application and explicit Q / R: not for ComplexF64. */
+int32_t dhqr_factor_batched_c64(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                double *dalpha, int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_solve_batched_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                               const double *dalpha, int64_t stride_alpha, double *db, int64_t strideb, int64_t batch);
+int32_t dhqr_qr_batched_c64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                            double *halpha, int64_t stride_alpha, int64_t batch, int32_t nb);
+int32_t dhqr_ldiv_batched_c64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                              const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
+                              int64_t stridex, int64_t batch);
 
 /* ------------------------------------------------------------------ Q application / metric
  * dB (m x nrhs) <- Q' dB (trans = 1) or Q dB (trans = 0), Q = H_1 ... H_n from a factored dA.

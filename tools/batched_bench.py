@@ -5,6 +5,11 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
        python tools/batched_bench.py --point M N BATCH     one point (what the children run)
        --dtype f32                                         the Float32 entry points (dhqr_*_f32: native kernels up to 64 x 32,
                                                            the promoted tier beyond), same points, same columns
+       --dtype c64                                         the ComplexF64 entry points (dhqr_factor_batched_c64 +
+                                                           dhqr_solve_batched_c64 against the loop of dhqr_factor_c64 +
+                                                           dhqr_solve_c64), at C64_SHAPES with batch 16384 unless --shapes /
+                                                           --batches say otherwise; no one-CU column: ComplexF64 has no
+                                                           one-workgroup tier
        --shapes 16x8,32x16                                 only these shapes (default: every shape of SHAPES)
        --nrhs K [--batches 16384]                          `H_k \\ B_k` with K right-hand sides per matrix instead: ONE
                                                            dhqr_solve_batched_nrhs_* call against the loop of K
@@ -36,6 +41,7 @@ SHAPES = [(12, 6), (16, 8), (32, 16), (64, 32), (110, 100), (220, 200)]
 BATCHES = [64, 1024, 16384]
 WARMUP, REPS = 3, 10
 ROUNDS, LOOP_BATCH = 5, 256  # --applyq
+C64_SHAPES, C64_BATCHES = [(16, 8), (40, 17), (64, 32)], [16384]  # --dtype c64
 
 
 def point(m, n, batch, dtype="f64"):
@@ -44,6 +50,8 @@ def point(m, n, batch, dtype="f64"):
     import __graft_entry__ as g
     pkg = g.import_package()
     batch = min(batch, (4 << 30) // (m * n * 8) - 1)  # the batch stays under 4 GiB
+    if dtype == "c64":
+        return point_c64(pkg, torch, m, n, batch)
     tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
     A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
     b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0", dtype=tdt).reshape(batch, m).contiguous()
@@ -96,6 +104,53 @@ def point(m, n, batch, dtype="f64"):
         ctx.close()
     else:
         assert torch.equal(x, b[:, :n]), "the one-workgroup tier must give the single calls' bits"
+    print("POINT " + json.dumps(out), flush=True)
+
+
+def point_c64(pkg, torch, m, n, batch):
+    """ComplexF64: one dhqr_factor_batched_c64 + one dhqr_solve_batched_c64 against dhqr_factor_c64 + dhqr_solve_c64 per
+    matrix on the same resident data"""
+    A0 = pkg.rand_colmajor_batched_c(batch, m, n, 1, "cuda:0")
+    b0 = pkg.rand_colmajor_batched_c(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    A, b = A0.clone(), b0.clone()
+    al = torch.zeros((batch, n), dtype=torch.complex128, device="cuda:0")
+    torch.cuda.synchronize()
+    L = pkg._lib.lib()
+    P = ctypes.c_void_p
+    pa, pal, pb, esz = A.data_ptr(), al.data_ptr(), b.data_ptr(), 16
+    os.environ["DHQR_SMALL"] = "1"
+
+    def measure(ctx, fn):
+        rates = []
+        for r in range(WARMUP + REPS):
+            A.copy_(A0)
+            b.copy_(b0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(ctx.handle)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(batch / dt)
+        return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
+
+    def batched(h):
+        pkg._lib.check(L.dhqr_factor_batched_c64(h, P(pa), m, n, m, m * n, P(pal), n, batch, 0))
+        pkg._lib.check(L.dhqr_solve_batched_c64(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), m, batch))
+
+    def looped(h):
+        for k in range(batch):
+            ak, alk = P(pa + esz * k * m * n), P(pal + esz * k * n)
+            pkg._lib.check(L.dhqr_factor_c64(h, ak, m, n, m, alk))
+            pkg._lib.check(L.dhqr_solve_c64(h, ak, m, n, m, alk, P(pb + esz * k * m)))
+
+    out = {"m": m, "n": n, "batch": batch, "dtype": "c64"}
+    ctx = pkg.Context(0)
+    out["batched"] = measure(ctx, batched)
+    x = b[:, :n].clone()
+    out["looped"] = measure(ctx, looped)
+    ctx.close()
+    assert ((x - b[:, :n]).abs().amax(dim=1) <= 1e-9 * x.abs().amax(dim=1)).all(), "batched and looped solutions differ"
     print("POINT " + json.dumps(out), flush=True)
 
 
@@ -294,7 +349,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--point", nargs=3, type=int)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--dtype", choices=("f64", "f32"), default="f64")
+    ap.add_argument("--dtype", choices=("f64", "f32", "c64"), default="f64")
     ap.add_argument("--shapes", default=None, help="e.g. 16x8,32x16 (default: every shape)")
     ap.add_argument("--nrhs", type=int, default=None, help="right-hand sides per matrix: the multi-column solve against the column loop")
     ap.add_argument("--applyq", choices=("t", "n", "q"), default=None, help="Q'B, QB or the explicit Q of a resident batched factor")
@@ -310,8 +365,10 @@ def main():
             point(*a.point, a.dtype)
         return 0
     t = a.dtype
-    shapes = SHAPES if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
-    batches = BATCHES if a.batches is None else [int(v) for v in a.batches.split(",")]
+    if t == "c64" and (a.nrhs is not None or a.applyq is not None):
+        ap.error("--dtype c64 has the factor + solve point only (ComplexF64 has no multi-column solve and no apply-Q)")
+    shapes = (C64_SHAPES if t == "c64" else SHAPES) if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
+    batches = (C64_BATCHES if t == "c64" else BATCHES) if a.batches is None else [int(v) for v in a.batches.split(",")]
     if a.applyq is not None:
         return main_applyq(a, shapes, batches if a.batches is not None else [16384])
     if a.nrhs is not None:
@@ -319,6 +376,8 @@ def main():
     lines = ["# tools/batched_bench.py: qr! + \\ of `batch` matrices, matrices per second, median (min .. max) of 10 repetitions",
              f"# batched = one dhqr_factor_batched_{t} + one dhqr_solve_batched_{t}; looped = batch x (dhqr_factor_{t} + dhqr_solve_{t}), small route on",
              "# one-CU = the batched calls with DHQR_TUNE batched_wave=0 (one workgroup per matrix) on the wave tier's shapes"]
+    if t == "c64":
+        lines[2] = "# (ComplexF64 has no one-workgroup tier: no one-CU column)"
     print("\n".join(lines), flush=True)
     for (m, n) in shapes:
         for batch in batches:
