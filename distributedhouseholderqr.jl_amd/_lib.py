@@ -120,6 +120,11 @@ SIGNATURES = {
     "dhqr_solve_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
     "dhqr_qr_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i32]),
     "dhqr_ldiv_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_solve_batched_nrhs_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64]),
+    "dhqr_ldiv_batched_nrhs_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_apply_q_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i32]),
+    "dhqr_form_q_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64]),
+    "dhqr_form_r_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64]),
     "dhqr_partialdot_c64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_partialdot_host_c64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_apply_q_f64": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i32]),

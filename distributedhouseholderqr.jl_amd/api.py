@@ -852,6 +852,122 @@ def get_q(H: DistributedHouseholderQRStruct):
     return Q if A.dim() == 3 else Q[0]
 
 
+# ------------------------------------------------------------------------------- the batched names, complex128 included
+# ldiv / ldiv_batched with a block of right-hand sides, apply_q_, get_q and get_r keep refusing a complex128 factor.  The four
+# functions below are named after the C entry points (dhqr_solve_batched_nrhs_* ... dhqr_form_r_batched_*) and take every
+# element type: complex128 goes to the _c64 entry points, float64 / float32 return exactly what the generic names return.
+def _c64_factor(H, what):
+    """(pointer, batch, m, n, lda, strideA) of a complex128 DEVICE factor: (batch, m, n) with column-major matrices, or one
+    column-major (m, n) matrix -- a batch of one"""
+    A = H.A
+    if not _is_tensor(A):
+        raise TypeError(f"device tensors only: the factor is a host array ({what} has no host form)")
+    if A.dim() not in (2, 3):
+        raise ValueError("(m, n) or (batch, m, n) factor expected")
+    return _colmajor_batch(A, "H.A")
+
+
+def _c64_alpha(H, batch, n):
+    A, α = H.A, H.α
+    if not _is_tensor(α) or α.dtype != A.dtype or not α.is_cuda or tuple(α.shape) != tuple(A.shape[:-2]) + (n,) or not α.is_contiguous():
+        raise TypeError(f"α must be a contiguous {A.dtype} CUDA tensor of shape {tuple(A.shape[:-2]) + (n,)}")
+    return ctypes.c_void_p(α.data_ptr())
+
+
+def solve_batched_nrhs(H: DistributedHouseholderQRStruct, B):
+    """`H \\ B` for a block of right-hand sides and every element type: B (batch, m, nrhs) with a batched factor, (m, nrhs)
+    with a single one -> X (batch, n, nrhs) / (n, nrhs), column-major.  B is NOT modified.  complex128:
+    dhqr_solve_batched_nrhs_c64 on a copy of a device B (its matrices column-major like the factor's),
+    dhqr_ldiv_batched_nrhs_c64 on numpy arrays (any layout; copied where the layout asks for it); column r of X has the bits
+    of ldiv_batched on the vectors B[..., r].  float64 / float32: ldiv(H, B)."""
+    A, α = H.A, H.α
+    _same_field(A, B, "B")
+    _same_field(A, α, "α")
+    if not _is_complex(A):
+        return ldiv(H, B)
+    if A.ndim not in (2, 3) or getattr(B, "ndim", 0) != A.ndim:
+        raise ValueError("B must have as many dimensions as the factor: (batch, m, nrhs) or (m, nrhs)")
+    L = _lib.lib()
+    single = A.ndim == 2
+    if _is_tensor(A):
+        ptr, batch, m, n, lda, strideA = _c64_factor(H, "a device solve")
+        if not _is_tensor(B) or B.dtype != A.dtype or tuple(B.shape[:-1]) != tuple(A.shape[:-2]) + (m,):
+            raise TypeError(f"B: {A.dtype} CUDA tensor of shape {tuple(A.shape[:-2]) + (m, 'nrhs')} expected")
+        _colmajor_batch(B, "B")  # (the layout rule, before the copy hides it)
+        _need_cuda(A, B)
+        nrhs = B.shape[-1]
+        W = empty_colmajor_batched_c(batch, m, nrhs, B.device)
+        W.copy_(B if not single else B.unsqueeze(0))  # src:318 copy of B
+        _call_small_family(A, L.dhqr_solve_batched_nrhs_c64, ptr, m, n, lda, strideA, _c64_alpha(H, batch, n), max(n, 1),
+                           ctypes.c_void_p(W.data_ptr()), nrhs, max(m, 1), max(m * nrhs, 1), batch)
+        X = empty_colmajor_batched_c(batch, n, nrhs, B.device)
+        X.copy_(W[:, :n, :])
+        return X[0] if single else X
+    if not isinstance(A, np.ndarray):
+        raise TypeError("complex128 numpy array or CUDA tensor expected")
+    A3 = A[None] if single else A
+    batch, m, n = A3.shape
+    B3 = np.asarray(B, dtype=np.complex128)
+    B3 = B3[None] if single else B3
+    if B3.shape[:2] != (batch, m):
+        raise ValueError(f"B must have shape {tuple(A.shape[:-2]) + (m, 'nrhs')}")
+    nrhs = B3.shape[2]
+    F, lda, strideA = _host_batch(A3)
+    Bf, ldb, strideB = _host_batch(B3)
+    al, sal = _host_rows(np.asarray(α).reshape(batch, n), batch, n, "α", np.complex128)
+    X = np.empty((batch, nrhs, n), dtype=np.complex128).transpose(0, 2, 1)
+    check(L.dhqr_ldiv_batched_nrhs_c64(get_context().handle, F.ctypes.data_as(ctypes.c_void_p), m, n, lda, strideA,
+                                       al.ctypes.data_as(ctypes.c_void_p), sal, Bf.ctypes.data_as(ctypes.c_void_p), nrhs, ldb, strideB,
+                                       X.ctypes.data_as(ctypes.c_void_p), max(n, 1), max(n * nrhs, 1), batch))
+    return X[0] if single else X
+
+
+def apply_q_batched_(H: DistributedHouseholderQRStruct, B, trans: bool):
+    """B <- Q^H B (trans) or Q B, in place, device tensors only, every element type: complex128 through
+    dhqr_apply_q_batched_c64 (a (batch, m, n) factor with B (batch, m, nrhs), or one matrix with B (m, nrhs), matrices
+    column-major); float64 / float32: apply_q_(H, B, trans)."""
+    A = H.A
+    _same_field(A, B, "B")
+    if not _is_complex(A):
+        return apply_q_(H, B, trans)
+    ptr, batch, m, n, lda, strideA = _c64_factor(H, "apply_q_batched_")
+    if not _is_tensor(B) or B.dtype != A.dtype or B.dim() != A.dim() or tuple(B.shape[:-1]) != tuple(A.shape[:-2]) + (m,):
+        raise TypeError(f"B: {A.dtype} CUDA tensor of shape {tuple(A.shape[:-2]) + (m, 'nrhs')} expected")
+    bptr, _, _, nrhs, ldb, strideB = _colmajor_batch(B, "B")
+    _need_cuda(A, B)
+    _call_small_family(A, _lib.lib().dhqr_apply_q_batched_c64, ptr, m, n, lda, strideA, bptr, nrhs, ldb, strideB, batch, 1 if trans else 0)
+    return B
+
+
+def form_q_batched(H: DistributedHouseholderQRStruct):
+    """explicit thin Q of a device factorisation of every element type: (batch, m, n) for a batch, (m, n) for one matrix,
+    column-major.  complex128: dhqr_form_q_batched_c64; float64 / float32: get_q(H)."""
+    A = H.A
+    if not _is_complex(A):
+        return get_q(H)
+    ptr, batch, m, n, lda, strideA = _c64_factor(H, "form_q_batched")
+    _need_cuda(A)
+    Q = empty_colmajor_batched_c(batch, m, n, A.device)
+    _call_small_family(A, _lib.lib().dhqr_form_q_batched_c64, ptr, m, n, lda, strideA, ctypes.c_void_p(Q.data_ptr()), max(m, 1),
+                       max(m * n, 1), batch)
+    return Q if A.dim() == 3 else Q[0]
+
+
+def form_r_batched(H: DistributedHouseholderQRStruct):
+    """n x n upper-triangular R of a device factorisation of every element type (strict upper part of H.A, α on the diagonal,
+    zeros below): (batch, n, n) or (n, n), column-major.  complex128: dhqr_form_r_batched_c64; float64 / float32: get_r(H)."""
+    A = H.A
+    _same_field(A, H.α, "α")
+    if not _is_complex(A):
+        return get_r(H)
+    ptr, batch, m, n, lda, strideA = _c64_factor(H, "form_r_batched")
+    _need_cuda(A)
+    R = empty_colmajor_batched_c(batch, n, n, A.device)
+    _call_small_family(A, _lib.lib().dhqr_form_r_batched_c64, ptr, m, n, lda, strideA, _c64_alpha(H, batch, n), max(n, 1),
+                       ctypes.c_void_p(R.data_ptr()), max(n, 1), max(n * n, 1), batch)
+    return R if A.dim() == 3 else R[0]
+
+
 def residual(H: DistributedHouseholderQRStruct, Aorig, work=None) -> float:
     """||Aorig - Q R||_F / ||Aorig||_F on the device (north-star metric)."""
     ptr, m, n, lda, dev = _dev_matrix(H.A)

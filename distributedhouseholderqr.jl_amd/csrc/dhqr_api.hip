@@ -1348,6 +1348,7 @@ int32_t dhqr_create(dhqr_ctx **out, int32_t device) {
     { long long v; if (tune_get("tn_min_tiles", &v)) c->tn_model_min_tiles = (int)v; }
     { long long v; if (tune_get("small_flags", &v)) c->small_flags = v != 0; }
     { long long v; if (tune_get("batched_wave", &v)) c->batched_wave = v != 0; }
+    { long long v; if (tune_get("znrhs_wave", &v)) c->znrhs_wave = v < 0 ? -1 : (v != 0); }
     { long long v; if (tune_get("short_panel_small", &v)) c->short_panel_small = v != 0; }
     { long long v; if (tune_get("partial_unblocked", &v)) c->partial_unblocked = v != 0; }
     { long long v; if (tune_get("partial_unblocked_max_rows", &v)) c->partial_unblocked_max_rows = v; }
@@ -2495,7 +2496,8 @@ int32_t dhqr_ldiv_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
 
 // ---- batches of small ComplexF64 matrices (dhqr.h: dhqr_factor_batched_c64 ...) ------------------------------------------
 // The argument rules are those of the Float64 batched family (check_batched), in complex elements; nb: 0 or DHQR_ZNB; device
-// pointers are 16-byte aligned.  Tiers and host forms: dhqr_batched_host.h; kernels: dhqr_batched_complex.h.
+// pointers are 16-byte aligned.  Tiers and host forms: dhqr_batched_host.h; kernels: dhqr_batched_complex.h,
+// dhqr_batched_complex_nrhs.h.
 static int32_t check_znb(int32_t nb) {
   if (nb != 0 && nb != DHQR_ZNB)
     return set_err(DHQR_EINVAL, "ComplexF64: nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_ZNB, nb);
@@ -2543,6 +2545,61 @@ int32_t dhqr_ldiv_batched_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t 
                    stride_alpha, reinterpret_cast<const double2 *>(hb), 1, m, strideb, reinterpret_cast<double2 *>(hx), n, stridex,
                    batch, BATCH, ONE_COLUMN);
 }
+
+// several right-hand sides, Q application, explicit Q and R (kernels: dhqr_batched_complex_nrhs.h, dhqr_batched_applyq.h)
+#define ZC(p_) reinterpret_cast<const double2 *>(p_)
+#define ZM(p_) reinterpret_cast<double2 *>(p_)
+int32_t dhqr_solve_batched_nrhs_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_block(dB, nrhs, ldb, strideB));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  CHECK(check_zptr(dB, "B"));
+  return solve_batched_nrhs(c, ZC(dA), m, n, lda, strideA, ZC(dalpha), stride_alpha, ZM(dB), nrhs, ldb, strideB, batch);
+}
+
+int32_t dhqr_ldiv_batched_nrhs_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const double *halpha, int64_t stride_alpha, const double *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, double *hX, int64_t ldx, int64_t strideX, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB),
+                rhs_block(hX, nrhs, ldx, strideX));
+  return ldiv_host(c, ZC(hA), m, n, lda, strideA, ZC(halpha), stride_alpha, ZC(hB), nrhs, ldb, strideB, ZM(hX), ldx, strideX, batch, BATCH,
+                   MULTI_COLUMN);
+}
+
+int32_t dhqr_apply_q_batched_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dB,
+                                 int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dB, nrhs, ldb, strideB), "B", trans);
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dB, "B"));
+  return apply_q_batched(c, ZC(dA), m, n, lda, strideA, ZM(dB), nrhs, ldb, strideB, batch, trans, APPLY_Q);
+}
+
+int32_t dhqr_form_q_batched_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dQ,
+                                int64_t ldq, int64_t strideQ, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED_Q(dA, m, n, lda, strideA, batch, rhs_block(dQ, n, ldq, strideQ), "Q", 0);
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dQ, "Q"));
+  return apply_q_batched(c, ZC(dA), m, n, lda, strideA, ZM(dQ), n, ldq, strideQ, batch, 0, FORM_Q);
+}
+
+int32_t dhqr_form_r_batched_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const double *dalpha, int64_t stride_alpha, double *dR, int64_t ldr, int64_t strideR, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_nrhs(dR, "R", n, n, ldr, strideR));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  CHECK(check_zptr(dR, "R"));
+  return form_r_batched(c, ZC(dA), n, lda, strideA, ZC(dalpha), stride_alpha, ZM(dR), ldr, strideR, batch);
+}
+#undef ZC
+#undef ZM
 
 int32_t dhqr_partialdot_c64(dhqr_ctx *c, const double *da, const double *db, int64_t lo, int64_t hi,
                             double *hout) {

@@ -28,8 +28,10 @@
 // tail group of 1 .. RG-1 columns loads zeros for the missing columns and stores nothing for them.
 //
 // k_batched_form_r: R_k (n x n) = the strict upper part of H_k, alpha_k on the diagonal, zeros written below (src:296-309);
-// k_batched_eye: [I; 0], the input of the explicit Q beyond the wave tier.  Plain element-wise kernels for every shape.
+// k_batched_eye: [I; 0], the input of the explicit Q beyond the wave tier.  Plain element-wise kernels for every shape and
+// every element type (ComplexF64: T = double2).
 #pragma once
+#include <type_traits>
 #include "dhqr_batched_nrhs.h"
 
 // Float64 columns per group.  Without alpha and 1 / alpha beside the matrix, NC = 16 holds four double-double chains under
@@ -153,8 +155,15 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQS_MIN_WAVES(NC)) void k_batched_a
   }
 }
 
+// the zero and the one of an element type (T = double, float; double2: a ComplexF64 element, re and im)
+template <typename T>
+__device__ __forceinline__ T bq_elem(double re) {
+  if constexpr (std::is_same_v<T, double2>) return make_double2(re, 0.0);
+  else return (T)re;
+}
+
 // R_k[i, j] = H_k[i, j] (i < j) | alpha_k[j] (i == j) | 0 (i > j) for i, j < n, k < batch: R_k at R + k strideR (leading
-// dimension ldr).  Consecutive threads take consecutive rows of a column; grid-stride.  T = double, float.
+// dimension ldr).  Consecutive threads take consecutive rows of a column; grid-stride.  T = double, float, double2.
 template <typename T>
 __global__ __launch_bounds__(256) void k_batched_form_r(const T *__restrict__ A, int64_t lda, int64_t strideA, int64_t n,
                                                         const T *__restrict__ alpha, int64_t stride_alpha, T *__restrict__ R,
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(256) void k_batched_form_r(const T *__restrict__ A,
   const int64_t per = n * n, total = per * batch;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t k = idx / per, r = idx - k * per, j = r / n, i = r - j * n;
-    T x = (T)0;
+    T x = bq_elem<T>(0.0);
     if (i < j) x = A[k * strideA + j * lda + i];
     else if (i == j) x = alpha[k * stride_alpha + j];
     R[k * strideR + j * ldr + i] = x;
@@ -170,11 +179,12 @@ __global__ __launch_bounds__(256) void k_batched_form_r(const T *__restrict__ A,
 }
 
 // Q_k <- [I; 0] (rows x cols) for k < batch: what the blocked route turns into the explicit Q
-__global__ __launch_bounds__(256) void k_batched_eye(double *__restrict__ Q, int64_t ldq, int64_t strideQ, int64_t rows, int64_t cols,
+template <typename T>
+__global__ __launch_bounds__(256) void k_batched_eye(T *__restrict__ Q, int64_t ldq, int64_t strideQ, int64_t rows, int64_t cols,
                                                      int64_t batch) {
   const int64_t per = rows * cols, total = per * batch;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t k = idx / per, r = idx - k * per, j = r / rows, i = r - j * rows;
-    Q[k * strideQ + j * ldq + i] = i == j ? 1.0 : 0.0;
+    Q[k * strideQ + j * ldq + i] = bq_elem<T>(i == j ? 1.0 : 0.0);
   }
 }

@@ -9,12 +9,15 @@
 // PROMOTED: widened into a Float64 workspace of the context, the Float64 route with the caller's nb, rounded back.
 // ComplexF64 (dhqr_factor_batched_c64 ... dhqr_ldiv_batched_c64): the wave tier -- one launch of the kernels of
 // dhqr_batched_complex.h -- | a host loop over dhqr_factor_c64_nb / dhqr_solve_c64; the host forms are those of the real types
-// with T = double2.
+// with T = double2.  Several right-hand sides, Q application, explicit Q and R (dhqr_solve_batched_nrhs_c64 ...
+// dhqr_form_r_batched_c64): the wave tier -- one launch of the kernels of dhqr_batched_complex_nrhs.h -- | the solve column
+// by column on the single-column route, Q on k_batched_zapplyq_general.
 // The host forms (qr_host, ldiv_host) end alike: after a failure of any step they still reach the final
 // hipStreamSynchronize -- nothing is left in flight on the caller's arrays -- and return the FIRST error.  (Before, the
 // single-column ldiv forms returned from a failed enqueue of the copy of X without it.)
 #pragma once
 #include <type_traits>
+#include "dhqr_batched_complex_nrhs.h"
 
 static int32_t pipe_error_check(dhqr_ctx *c);  // (dhqr_api.hip, below this file's inclusion)
 
@@ -154,6 +157,8 @@ static int32_t wave_solve_nrhs(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, i
   CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
   if constexpr (std::is_same_v<T, double>)
     WAVE_LAUNCH(k_batched_ldiv_wave_nrhs, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
+  else if constexpr (std::is_same_v<T, double2>)
+    WAVE_LAUNCH(k_batched_zldiv_wave_nrhs, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
   else
     WAVE_LAUNCH(k_batched_ldiv_wave_nrhs_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
   return prof_end(c);
@@ -174,6 +179,7 @@ static int32_t wave_apply_q(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int6
       WAVE_LAUNCH_T(kernel_, WAVE_TARGS(0), n, batch, dA, lda, strideA, (int)m, (int)n, dB, (int)nrhs, ldb, strideB, batch);    \
   } while (0)
   if constexpr (std::is_same_v<T, double>) APPLYQ_LAUNCH(k_batched_applyq_wave);
+  else if constexpr (std::is_same_v<T, double2>) APPLYQ_LAUNCH(k_batched_zapplyq_wave);
   else APPLYQ_LAUNCH(k_batched_applyq_wave_s);
 #undef APPLYQ_LAUNCH
   return prof_end(c);
@@ -367,11 +373,29 @@ template <typename T>
 static int32_t apply_q_batched(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dB, int64_t nrhs,
                                int64_t ldb, int64_t strideB, int64_t batch, int trans, bool formq) {
   if (batched_wave_fit(c, m, n)) return wave_apply_q(c, dA, m, n, lda, strideA, dB, nrhs, ldb, strideB, batch, trans, formq);
-  if constexpr (std::is_same_v<T, double>) {
+  if constexpr (std::is_same_v<T, double2>) {
+    // ComplexF64 has no blocked apply-Q: [I; 0] for the explicit Q, then ONE launch of the plain kernel, a workgroup per
+    // (matrix, column of B) on a 1-D grid (batch * nrhs may exceed a y dimension)
+    if (batch * nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch * nrhs = %lld too large", (long long)(batch * nrhs));
+    if (formq) {
+      const int64_t total = m * nrhs * batch;
+      hipLaunchKernelGGL(k_batched_eye<double2>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream,
+                         dB, ldb, strideB, m, nrhs, batch);
+      LAUNCHCHECK();
+    }
+    CHECK(prof_begin(c, CAT_SOLVE));
+    const dim3 grid((unsigned)(batch * nrhs)), block(BQZG_THREADS);
+    if (trans)
+      hipLaunchKernelGGL(k_batched_zapplyq_general<1>, grid, block, 0, c->stream, dA, lda, strideA, m, n, dB, nrhs, ldb, strideB);
+    else
+      hipLaunchKernelGGL(k_batched_zapplyq_general<0>, grid, block, 0, c->stream, dA, lda, strideA, m, n, dB, nrhs, ldb, strideB);
+    LAUNCHCHECK();
+    return prof_end(c);
+  } else if constexpr (std::is_same_v<T, double>) {
     CHECK(check_mat(dB, m, nrhs, ldb, false));  // (the blocked route's limit on a leading dimension; dA: check_batch)
     if (formq) {
       const int64_t total = m * nrhs * batch;
-      hipLaunchKernelGGL(k_batched_eye, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dB,
+      hipLaunchKernelGGL(k_batched_eye<double>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dB,
                          ldb, strideB, m, nrhs, batch);
       LAUNCHCHECK();
     }
@@ -385,7 +409,7 @@ static int32_t apply_q_batched(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, i
   }
 }
 
-// one element-wise launch for every shape and both element types (copies: nothing to promote)
+// one element-wise launch for every shape and every element type (copies: nothing to promote)
 template <typename T>
 static int32_t form_r_batched(dhqr_ctx *c, const T *dA, int64_t n, int64_t lda, int64_t strideA, const T *dalpha, int64_t stride_alpha,
                               T *dR, int64_t ldr, int64_t strideR, int64_t batch) {
@@ -431,6 +455,29 @@ static int32_t solve_batched(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t 
   CHECK(prof_begin(c, CAT_SOLVE));
   WAVE_LAUNCH(k_batched_zldiv_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
   return prof_end(c);
+}
+
+// Does the complex multi-column kernel pay?  Measured on the MI355X (profiles/batched_c64_nrhs_throughput.txt: batch 16384,
+// resident factor, 16 x 8 / 40 x 17 / 64 x 32, groups of BQZN_RG = 1 / 2 / 4, K = 2, 4, 8, 16 columns, five rounds of ten
+// repetitions; the kernel over the loop of K dhqr_solve_batched_c64 calls, round by round).  Its time goes by GROUPS, like
+// the real kernel's: a group costs 0.92 / 1.8 / 3.5 single-column solves, whether its columns are real or the zeros of a
+// tail.  K = 2 is 1.01 - 1.04 x at 16 x 8 -- inside the 3 % the ratio moves from round to round -- and 0.55 - 0.56 x at
+// the other two shapes; K = 4, 8 and 16, all of them full groups, win at every shape and in every round: 1.04 - 1.08 x,
+// 1.07 - 1.12 x, 1.09 - 1.15 x (the first round of a process at the two smaller shapes, 1.01 - 1.06 x, aside).  No call with a tail group was measured.
+// So: the kernel for at least four columns in full groups, the column loop -- the same bits -- for every other call.
+// (DHQR_TUNE znrhs_wave=1 / 0: always the kernel / the loop, for measurements and for the tests of the tail groups.)
+static inline bool znrhs_wave_pays(int64_t nrhs, int64_t n) { return nrhs >= 4 && nrhs % BQZN_RG(wave_nc(n)) == 0; }
+
+// The wave tier where it pays: the multi-column kernel.  Every other call: the single-column route, column by column -- its
+// tiers, its synchronisation, its profiling counts, its bits (a column of complex elements stays 16-byte aligned).
+static int32_t solve_batched_nrhs(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                  const double2 *dalpha, int64_t stride_alpha, double2 *dB, int64_t nrhs, int64_t ldb, int64_t strideB,
+                                  int64_t batch) {
+  if (batched_wave_fit(c, m, n) && (c->znrhs_wave < 0 ? znrhs_wave_pays(nrhs, n) : c->znrhs_wave != 0))
+    return wave_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+  for (int64_t r = 0; r < nrhs; ++r)
+    CHECK(solve_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
+  return DHQR_OK;
 }
 
 // ---- the host forms ------------------------------------------------------------------------------------------------------
@@ -508,13 +555,9 @@ static int32_t ldiv_host(dhqr_ctx *c, const T *hA, int64_t m, int64_t n, int64_t
   int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
   if (rc == DHQR_OK) rc = batch_copy(c, dal, halpha, n, 1, n, stride_alpha, batch, true);
   if (rc == DHQR_OK) rc = batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true);  // src:318 copy of B
-  if (rc == DHQR_OK) {
-    if constexpr (std::is_same_v<T, double2>)  // (ComplexF64 has the single-column solve only)
-      rc = solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
-    else
-      rc = multi ? solve_batched_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch)
-                 : solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
-  }
+  if (rc == DHQR_OK)
+    rc = multi ? solve_batched_nrhs(c, dA, m, n, m, m * n, dal, n, dB, nrhs, m, m * nrhs, batch)
+               : solve_batched(c, dA, m, n, m, m * n, dal, n, dB, m, batch, single);
   if (rc == DHQR_OK) rc = host_finish(c, rc, true);  // (the serial tier's solves may have been repeated: dhqr.h)
   if (rc == DHQR_OK)  // src:320: X_k = the first n rows of B_k
     rc = batch_copy(c, dB, m, m * nrhs, hX, ldx, strideX, n, nrhs, batch, false);

@@ -19,7 +19,7 @@
 #   reference                                 this module
 #   qr!(A)                      src:311-315   qr!(A; nb=default_nb(A))      -> dhqr_qr_f64
 #   H \ b                       src:317-321   \(H, b)                       -> dhqr_ldiv_f64
-#   H \ B (B a Matrix)          (new)         \(H, B)                       -> dhqr_ldiv_batched_nrhs_f64 / _f32
+#   H \ B (B a Matrix)          (new)         \(H, B)                       -> dhqr_ldiv_batched_nrhs_f64 / _f32 / _c64
 #   householder!(A, α)          src:113       householder!(A, α; nb=...)    -> dhqr_qr_f64
 #   solve_householder!(b, H, α) src:284-294   solve_householder!(b, H, α)   -> dhqr_ldiv_f64
 #   partialdot(a, b, is, T)     src:42-49     partialdot(a, b, is, Float64) -> dhqr_partialdot_host_f64 (KAT hook)
@@ -170,6 +170,21 @@ function LinearAlgebra.:(\)(H::DistributedHouseholderQRStruct{<:StridedMatrix{Fl
   check(ccall((:dhqr_ldiv_batched_nrhs_f32, libdhqr), Int32,
               (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Int64, Int64,
                Ptr{Float32}, Int64, Int64, Int64),
+              context(), H.A, m, n, stride(H.A, 2), max(stride(H.A, 2) * (n - 1) + m, 1), H.α, max(n, 1),
+              B, nrhs, max(m, 1), max(m * nrhs, 1), X, max(n, 1), max(n * nrhs, 1), 1))
+  return X
+end
+
+# ComplexF64 (a Ptr{ComplexF64} is the library's interleaved (re, im) `double *`; leading dimensions and strides count
+# complex elements): column r of X has the bits of dhqr_ldiv_batched_c64 (batch = 1) on B[:, r]
+function LinearAlgebra.:(\)(H::DistributedHouseholderQRStruct{<:StridedMatrix{ComplexF64}}, B::Matrix{ComplexF64})
+  m, n = size(H.A)
+  size(B, 1) == m || throw(DimensionMismatch("B has $(size(B, 1)) rows, the factor $m"))
+  nrhs = size(B, 2)
+  X = Matrix{ComplexF64}(undef, n, nrhs)
+  check(ccall((:dhqr_ldiv_batched_nrhs_c64, libdhqr), Int32,
+              (Ptr{Cvoid}, Ptr{ComplexF64}, Int64, Int64, Int64, Int64, Ptr{ComplexF64}, Int64, Ptr{ComplexF64}, Int64, Int64, Int64,
+               Ptr{ComplexF64}, Int64, Int64, Int64),
               context(), H.A, m, n, stride(H.A, 2), max(stride(H.A, 2) * (n - 1) + m, 1), H.α, max(n, 1),
               B, nrhs, max(m, 1), max(m * nrhs, 1), X, max(n, 1), max(n * nrhs, 1), 1))
   return X

@@ -454,7 +454,7 @@ int32_t dhqr_partialdot_host_c64(dhqr_ctx *ctx, const double *ha, const double *
  *                            modified (src:318).
  * batch == 0 or n == 0: no-op that looks at no pointer, DHQR_OK.  DHQR_EINVAL, and nothing is written: batch < 0, m < n,
  * lda < m, strideA < lda*(n-1) + m, stride_alpha < n, strideb < m, stridex < n, null pointers, another nb, a device pointer
- * that is not 16-byte aligned.  Several right-hand sides per matrix, Q application and explicit Q / R: not for ComplexF64. */
+ * that is not 16-byte aligned.  Several right-hand sides per matrix, Q application and explicit Q / R: the next section. */
 int32_t dhqr_factor_batched_c64(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                 double *dalpha, int64_t stride_alpha, int64_t batch, int32_t nb);
 int32_t dhqr_solve_batched_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
@@ -464,6 +464,51 @@ int32_t dhqr_qr_batched_c64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int
 int32_t dhqr_ldiv_batched_c64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                               const double *halpha, int64_t stride_alpha, const double *hb, int64_t strideb, double *hx,
                               int64_t stridex, int64_t batch);
+
+/* ------------------------------------------------------------------ batches of small ComplexF64 factors: several
+ * right-hand sides, Q application, explicit Q and R
+ * The ComplexF64 counterparts of dhqr_solve_batched_nrhs_f64, dhqr_ldiv_batched_nrhs_f64, dhqr_apply_q_batched_f64,
+ * dhqr_form_q_batched_f64 and dhqr_form_r_batched_f64: the same argument lists, the same layouts (B_k, Q_k, R_k, X_k at
+ * p + k stride with their own leading dimension), the same argument rules and empty cases, with the conventions of the
+ * ComplexF64 section -- pointers are interleaved (re, im) doubles, EVERY leading dimension and stride counts complex
+ * elements, device pointers are 16-byte aligned.  A single matrix is a batch of one.  Q = H_1 ... H_n with the Hermitian
+ * reflectors H_c = I - v_c v_c^H of the factor; trans = 1 applies Q^H.
+ *   dhqr_solve_batched_nrhs_c64  dB_k (m x nrhs) <- [X_k; tail of Q^H B_k], in place.  Column r has the BITS of
+ *                            dhqr_solve_batched_c64 on that column alone, whatever nrhs and batch.  m <= 64 and n <= 32
+ *                            (small route on): ONE launch of the multi-column kernel (csrc/dhqr_batched_complex_nrhs.h: the
+ *                            factor and alpha in registers once, the columns in groups of 1 / 2 / 4 for n <= 8 / 16 / 32)
+ *                            where that was measured to beat the column loop -- nrhs >= 4 in full groups: 1.04 - 1.15 x,
+ *                            profiles/batched_c64_nrhs_throughput.txt --, else, and at every other shape,
+ *                            dhqr_solve_batched_c64 column by column: its tiers, synchronisation and counts.
+ *   dhqr_ldiv_batched_nrhs_c64   host in / host out through the staging area of dhqr_ldiv_batched_c64; hB is not modified
+ *                            (src:318); X_k (n x nrhs) has the device form's bits.  Synchronous.
+ *   dhqr_apply_q_batched_c64 dB_k <- Q_k^H dB_k (trans = 1) or Q_k dB_k (trans = 0), in place; needs no alpha.
+ *   dhqr_form_q_batched_c64  dQ_k (m x n, ldq) <- the explicit thin Q_k; nothing of dQ is read.
+ *                            Both: m <= 64 and n <= 32 (small route on) ONE launch, one wave per matrix, a column carried in
+ *                            double-double per component; rows n .. m-1 of trans = 1 have the bits of what the solve leaves
+ *                            there; form_q compares equal to trans = 0 on [I; 0] for a finite factor.  Everything else, and
+ *                            every shape with the small route off: ONE launch of a plain kernel, a workgroup per (matrix,
+ *                            column), in place in device memory in plain double (form_q: [I; 0] first); it re-reads the
+ *                            factor once per column -- a blocked ComplexF64 apply-Q for large matrices does not exist yet.
+ *                            Asynchronous on the ctx stream; with profiling on each launch counts one n_solve group.
+ *   dhqr_form_r_batched_c64  dR_k (n x n, ldr) <- the strict upper part of H_k, alpha_k on the diagonal, zeros below: one
+ *                            element-wise launch for every shape.  Asynchronous.
+ * nrhs == 0, batch == 0 or n == 0: no-op that looks at no pointer.  DHQR_EINVAL, and nothing is written: what the Float64
+ * namesakes reject (negative nrhs or batch, trans not 0 or 1, m < n, short leading dimensions or strides, null pointers) and
+ * a device pointer that is not 16-byte aligned. */
+int32_t dhqr_solve_batched_nrhs_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                    const double *dalpha, int64_t stride_alpha, double *dB, int64_t nrhs, int64_t ldb,
+                                    int64_t strideB, int64_t batch);
+int32_t dhqr_ldiv_batched_nrhs_c64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                   const double *halpha, int64_t stride_alpha, const double *hB, int64_t nrhs, int64_t ldb,
+                                   int64_t strideB, double *hX, int64_t ldx, int64_t strideX, int64_t batch);
+int32_t dhqr_apply_q_batched_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                 double *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch, int32_t trans);
+int32_t dhqr_form_q_batched_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                double *dQ, int64_t ldq, int64_t strideQ, int64_t batch);
+int32_t dhqr_form_r_batched_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                const double *dalpha, int64_t stride_alpha, double *dR, int64_t ldr, int64_t strideR,
+                                int64_t batch);
 
 /* ------------------------------------------------------------------ Q application / metric
  * dB (m x nrhs) <- Q' dB (trans = 1) or Q dB (trans = 0), Q = H_1 ... H_n from a factored dA.

@@ -9,7 +9,10 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
                                                            dhqr_solve_batched_c64 against the loop of dhqr_factor_c64 +
                                                            dhqr_solve_c64), at C64_SHAPES with batch 16384 unless --shapes /
                                                            --batches say otherwise; no one-CU column: ComplexF64 has no
-                                                           one-workgroup tier
+                                                           one-workgroup tier.  With --nrhs K: the multi-column KERNEL
+                                                           (DHQR_TUNE znrhs_wave=1) against the loop of K
+                                                           dhqr_solve_batched_c64 calls, and the library's own rule, ROUNDS
+                                                           rounds each.  With --applyq: as for the real types
        --shapes 16x8,32x16                                 only these shapes (default: every shape of SHAPES)
        --nrhs K [--batches 16384]                          `H_k \\ B_k` with K right-hand sides per matrix instead: ONE
                                                            dhqr_solve_batched_nrhs_* call against the loop of K
@@ -154,18 +157,27 @@ def point_c64(pkg, torch, m, n, batch):
     print("POINT " + json.dumps(out), flush=True)
 
 
+def _makers(pkg, torch, dtype):
+    """(random batch, empty batch, element size) of a dtype: (batch, rows, cols) device tensors with column-major matrices"""
+    if dtype == "c64":
+        return pkg.rand_colmajor_batched_c, pkg.empty_colmajor_batched_c, 16
+    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    return (lambda b, r, c, seed, dev: pkg.rand_colmajor_batched(b, r, c, seed, dev, dtype=tdt),
+            lambda b, r, c, dev: pkg.empty_colmajor_batched(b, r, c, dev, dtype=tdt), esz)
+
+
 def point_nrhs(m, n, batch, nrhs, dtype="f64"):
     """solve only: the factor stays resident; per repetition B is restored, then ONE multi-column call or K single-column ones"""
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as g
     pkg = g.import_package()
-    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    rand, empty, esz = _makers(pkg, torch, dtype)
     os.environ["DHQR_SMALL"] = "1"
-    A = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
-    B0 = pkg.empty_colmajor_batched(batch, m, nrhs, "cuda:0", dtype=tdt)
+    A = rand(batch, m, n, 1, "cuda:0")
+    B0 = empty(batch, m, nrhs, "cuda:0")
     for r in range(nrhs):
-        B0[:, :, r] = pkg.rand_colmajor_batched(batch, m, 1, 7 + 1000 * r, "cuda:0", dtype=tdt).reshape(batch, m)
+        B0[:, :, r] = rand(batch, m, 1, 7 + 1000 * r, "cuda:0").reshape(batch, m)
     B = B0.clone(memory_format=torch.preserve_format)
     assert B.stride() == B0.stride() == (m * nrhs, 1, m)
     H = pkg.qr_batched_(A)
@@ -197,6 +209,26 @@ def point_nrhs(m, n, batch, nrhs, dtype="f64"):
             pkg._lib.check(solve_1(h, P(pa), m, n, m, m * n, P(pal), n, P(pb + esz * r * m), m * nrhs, batch))
 
     out = {"m": m, "n": n, "batch": batch, "nrhs": nrhs, "dtype": dtype}
+    if dtype == "c64":
+        # the library sends a ComplexF64 call to the multi-column kernel or to the column loop by a speed rule; what the rule
+        # is derived from is the KERNEL against the loop, so the kernel is forced here (DHQR_TUNE znrhs_wave=1, read when a
+        # context is created) and the rule's own choice measured beside it; ROUNDS rounds each, for the spread
+        os.environ["DHQR_TUNE"] = "znrhs_wave=1"
+        forced = pkg.Context(0)
+        del os.environ["DHQR_TUNE"]
+        ctx = pkg.Context(0)
+        out["kernel"], out["column_loop_rounds"], out["rule"] = [], [], []
+        for _ in range(ROUNDS):
+            out["kernel"].append(measure(forced, multi))
+            X = B.clone()
+            out["column_loop_rounds"].append(measure(ctx, columns))
+            assert torch.equal(X, B), "the multi-column kernel and the loop over the columns must give the same bits"
+            out["rule"].append(measure(ctx, multi))
+            assert torch.equal(X, B)
+        forced.close()
+        ctx.close()
+        print("POINT " + json.dumps(out), flush=True)
+        return
     ctx = pkg.Context(0)
     out["nrhs_call"] = measure(ctx, multi)
     X = B.clone()
@@ -212,17 +244,17 @@ def point_applyq(m, n, batch, nrhs, op, dtype="f64"):
     import torch
     import __graft_entry__ as g
     pkg = g.import_package()
-    tdt, esz = (torch.float32, 4) if dtype == "f32" else (torch.float64, 8)
+    rand, empty, esz = _makers(pkg, torch, dtype)
     os.environ["DHQR_SMALL"] = "1"
     cols = n if op == "q" else nrhs
-    A = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dtype=tdt)
-    B0 = pkg.empty_colmajor_batched(batch, m, cols, "cuda:0", dtype=tdt)
+    A = rand(batch, m, n, 1, "cuda:0")
+    B0 = empty(batch, m, cols, "cuda:0")
     if op == "q":
         B0.zero_()
         B0.diagonal(dim1=1, dim2=2).fill_(1.0)  # [I; 0]: what the loop of single calls starts from
     else:
         for r in range(cols):
-            B0[:, :, r] = pkg.rand_colmajor_batched(batch, m, 1, 7 + 1000 * r, "cuda:0", dtype=tdt).reshape(batch, m)
+            B0[:, :, r] = rand(batch, m, 1, 7 + 1000 * r, "cuda:0").reshape(batch, m)
     B = B0.clone(memory_format=torch.preserve_format)
     assert B.stride() == B0.stride() == (m * cols, 1, m)
     H = pkg.qr_batched_(A)
@@ -266,7 +298,7 @@ def point_applyq(m, n, batch, nrhs, op, dtype="f64"):
     for _ in range(ROUNDS):
         out["new"].append(measure(ctx, new, batch))
         out["solve"].append(measure(ctx, solve, batch))
-        if dtype == "f64":
+        if dtype == "f64":  # (dhqr_apply_q_f64: Float64 alone has a single-matrix apply-Q to loop over)
             out["looped"].append(measure(ctx, looped, lb))
     ctx.close()
     print("POINT " + json.dumps(out), flush=True)
@@ -320,6 +352,11 @@ def main_nrhs(a, shapes, batches):
     t, K = a.dtype, a.nrhs
     lines = [f"# tools/batched_bench.py --nrhs {K} --dtype {t}: H_k \\ B_k, {K} right-hand sides per matrix, resident factor; median (min .. max) of 10 repetitions",
              f"# nrhs call = one dhqr_solve_batched_nrhs_{t}; column loop = {K} x dhqr_solve_batched_{t} on the columns of the same B (the same bits, asserted)"]
+    if t == "c64":
+        lines[0] = (f"# tools/batched_bench.py --nrhs {K} --dtype c64: H_k \\ B_k, {K} right-hand sides per matrix, resident factor; matrices per second; "
+                    f"{ROUNDS} rounds of {REPS} repetitions in one process, every round's median, then min .. max over all repetitions")
+        lines[1] = (f"# kernel = one dhqr_solve_batched_nrhs_c64 with DHQR_TUNE znrhs_wave=1 (always the multi-column kernel); column loop = {K} x "
+                    "dhqr_solve_batched_c64 on the columns of the same B (the same bits, asserted); the library's rule = the same call, default context")
     print("\n".join(lines), flush=True)
     for (m, n) in shapes:
         for batch in batches:
@@ -334,6 +371,16 @@ def main_nrhs(a, shapes, batches):
                         f.write("\n".join(lines) + "\n")
                 return 1
             r = json.loads(row[0][6:])
+            if t == "c64":
+                med = lambda rs: statistics.median(x["median"] for x in rs)
+                rounds = lambda rs: " ".join(f"{x['median']:.0f}" for x in rs) + f" ({min(x['min'] for x in rs):.0f} .. {max(x['max'] for x in rs):.0f})"
+                ratios = [k["median"] / c["median"] for k, c in zip(r["kernel"], r["column_loop_rounds"])]
+                txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} nrhs {K:3d} c64 | kernel {rounds(r['kernel'])} | column loop {rounds(r['column_loop_rounds'])} | "
+                       f"kernel/loop per round {' '.join(f'{x:.3f}' for x in ratios)} | median {med(r['kernel']) / med(r['column_loop_rounds']):5.2f}x | "
+                       f"the library's rule {rounds(r['rule'])}")
+                lines.append(txt)
+                print(txt, flush=True)
+                continue
             new, old = r["nrhs_call"], r["column_loop"]
             txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} nrhs {K:3d} {t} | nrhs call {fmt(new)} matrices/s {new['median'] * K:13.0f} rhs/s | "
                    f"column loop {fmt(old)} matrices/s {old['median'] * K:13.0f} rhs/s | nrhs/loop {new['median'] / old['median']:6.2f}x")
@@ -365,8 +412,6 @@ def main():
             point(*a.point, a.dtype)
         return 0
     t = a.dtype
-    if t == "c64" and (a.nrhs is not None or a.applyq is not None):
-        ap.error("--dtype c64 has the factor + solve point only (ComplexF64 has no multi-column solve and no apply-Q)")
     shapes = (C64_SHAPES if t == "c64" else SHAPES) if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
     batches = (C64_BATCHES if t == "c64" else BATCHES) if a.batches is None else [int(v) for v in a.batches.split(",")]
     if a.applyq is not None:
