@@ -287,7 +287,9 @@ class DistributedHouseholderQRStruct:
 
 
 def _householder_c64(A, α, nb=0):
-    """ComplexF64 method of householder! (src:9, 51-59, 122-148, 171-213): nb = 0 unblocked, 64 blocked."""
+    """ComplexF64 method of householder! (src:9, 51-59, 122-148, 171-213): nb = 0 unblocked, 64 blocked.  Up to 128 rows with
+    the small route on, whatever nb: ONE launch (the batched tiers on a batch of one; host arrays through the context's
+    pinned staging buffer)."""
     L = _lib.lib()
     if _is_tensor(A):
         ptr, m, n, lda, dev = _dev_matrix(A, torch.complex128)
@@ -569,7 +571,8 @@ def qr_batched_(A, nb: Optional[int] = None) -> DistributedHouseholderQRStruct:
     serial loop beyond.  A is a CUDA tensor whose matrices are column-major (empty_colmajor_batched) or a numpy array; a
     host array in another layout is copied to that layout and back.  Mutates A; returns the struct with α of shape (batch, n).
     float32: dhqr_*_batched_f32.  complex128 (empty_colmajor_batched_c): dhqr_factor_batched_c64 / dhqr_qr_batched_c64 -- one
-    wave per matrix up to 64 x 32, a serial loop of single factorisations beyond; nb is None, 0 or ZNB (_resolve_nb)."""
+    wave per matrix up to 64 x 32, one workgroup per matrix up to 128 rows (both one asynchronous launch, nb ignored), a
+    serial loop of single factorisations beyond; nb is None, 0 or ZNB (_resolve_nb)."""
     L = _lib.lib()
     if A.ndim != 3:
         raise ValueError("(batch, m, n) array expected")

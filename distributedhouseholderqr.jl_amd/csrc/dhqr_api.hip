@@ -2212,7 +2212,15 @@ static int32_t check_zptr(const void *p, const char *what) {
   return DHQR_OK;
 }
 
-int32_t dhqr_factor_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, double *dalpha) {
+static int32_t check_znb(int32_t nb) {
+  if (nb != 0 && nb != DHQR_ZNB)
+    return set_err(DHQR_EINVAL, "ComplexF64: nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_ZNB, nb);
+  return DHQR_OK;
+}
+
+// The unblocked factorisation of every size: what dhqr_factor_c64 runs beyond the one-workgroup route, and what the panels
+// of the blocked, column-split and multi-GPU drivers (zpanel_make) run whatever their size.
+static int32_t zfactor_unblocked(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, double *dalpha) {
   ENTER(c);
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(dA, m, n, lda, true));
@@ -2263,10 +2271,23 @@ int32_t dhqr_factor_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t l
   return DHQR_OK;
 }
 
+// The entry point: up to 128 rows with the small route on, ONE launch on the ctx stream -- a batch of one on the tiers of
+// dhqr_factor_batched_c64 (dhqr_batched_host.h: the wave kernel up to 64 x 32, k_small_zqr beyond), so the bits of that call.
+int32_t dhqr_factor_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, double *dalpha) {
+  ENTER(c);
+  if (no_columns(m, n)) return DHQR_OK;
+  CHECK(check_mat(dA, m, n, lda, true));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  if (small_zfit(c, m, n))
+    return factor_batched(c, reinterpret_cast<double2 *>(dA), m, n, lda, 0, reinterpret_cast<double2 *>(dalpha), 0, 1, 0);
+  return zfactor_unblocked(c, dA, m, n, lda, dalpha);
+}
+
 // One ComplexF64 panel: factor (src:122-148,171-213 inside the panel) and, when `build` is set, embed its reflectors as a
 // real 2 rows x 128 operand and build T (the last panel is applied to nothing: build = false).
 static int32_t zpanel_make(dhqr_ctx *c, double *P, int64_t rows, int64_t w, int64_t lda, double *al, const PanelBuf &pb, bool build) {
-  CHECK(dhqr_factor_c64(c, P, rows, w, lda, al));
+  CHECK(zfactor_unblocked(c, P, rows, w, lda, al));
   if (!build) return DHQR_OK;
   const int64_t npad = panel_ldv(2 * rows);
   CHECK(prof_begin(c, CAT_TBUILD));
@@ -2292,6 +2313,7 @@ int32_t dhqr_factor_c64_nb(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_
   CHECK(check_mat(dA, m, n, lda, true));
   CHECK(check_zptr(dA, "matrix"));
   CHECK(check_zptr(dalpha, "alpha"));
+  if (small_zfit(c, m, n)) return dhqr_factor_c64(c, dA, m, n, lda, dalpha);  // the one-workgroup route, whatever nb says
   const int64_t ZB = DHQR_ZNB;
   CHECK(ensure(c, c->vt, 2 * (size_t)panel_elems(2 * m)));  // two panel operand buffers (look-ahead: panel k + 1 is built while k is applied)
   double *vtb[2] = {c->vt.p, c->vt.p + panel_elems(2 * m)};
@@ -2377,11 +2399,37 @@ int32_t dhqr_factor_c64_nb(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_
   return DHQR_OK;
 }
 
+// The host-array calls on the one-workgroup route (small_zfit), in the form of dhqr_qr_f64 / dhqr_ldiv_f64: memcpy into the
+// context's pinned staging buffer -> ONE launch that reads and writes it across PCIe itself -> the pinned completion word
+// (the wave kernels up to 64 x 32 have none: the stream's synchronisation) -> memcpy.  No hipMalloc, no hipMemcpy; the bits
+// of the device-resident call (the same launch).
+static int32_t zqr_host_small(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, double *halpha) {
+  const size_t na = (size_t)m * (size_t)n;
+  CHECK(small_pin_ensure(c, 2 * (na + (size_t)n)));
+  double2 *pA = reinterpret_cast<double2 *>(c->small_pin), *pal = pA + na;
+  unsigned long long *done = reinterpret_cast<unsigned long long *>(c->small_pin + c->small_pin_cap);
+  copy_cols(c->small_pin, 2 * m, hA, 2 * lda, 2 * m, n);
+  if (batched_wave_fit(c, m, n)) {
+    CHECK(factor_batched(c, pA, m, n, m, 0, pal, 0, 1, 0));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+  } else {
+    CHECK(small_zqr(c, pA, m, pA, m, m, n, pal, done, ++c->small_epoch, SmallBatch()));
+    CHECK(small_wait_done(c, done, c->small_epoch));
+  }
+  copy_cols(hA, 2 * lda, c->small_pin, 2 * m, 2 * m, n);
+  memcpy(halpha, pal, (size_t)n * sizeof(double2));
+  return DHQR_OK;
+}
+
 int32_t dhqr_qr_c64_nb(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, double *halpha, int32_t nb) {
   ENTER(c);
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(hA, m, n, lda, true));
   if (!halpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  if (small_zfit(c, m, n)) {  // (whatever nb says, as on the device)
+    CHECK(check_znb(nb));
+    return zqr_host_small(c, hA, m, n, lda, halpha);
+  }
   double *dA = nullptr, *dal = nullptr;
   const size_t esz = 2 * sizeof(double);
   if (hipMalloc((void **)&dA, (size_t)m * n * esz) != hipSuccess)
@@ -2410,6 +2458,7 @@ int32_t dhqr_qr_c64(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, 
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(hA, m, n, lda, true));
   if (!halpha) return set_err(DHQR_EINVAL, "null alpha pointer");
+  if (small_zfit(c, m, n)) return zqr_host_small(c, hA, m, n, lda, halpha);
   double *dA = nullptr, *dal = nullptr;
   const size_t esz = 2 * sizeof(double);
   if (hipMalloc((void **)&dA, (size_t)m * n * esz) != hipSuccess)
@@ -2443,6 +2492,8 @@ int32_t dhqr_solve_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int6
   CHECK(check_zptr(db, "b"));
   const double2 *A = reinterpret_cast<const double2 *>(dA), *al = reinterpret_cast<const double2 *>(dalpha);
   double2 *b = reinterpret_cast<double2 *>(db);
+  // up to 128 rows with the small route on: ONE launch, a batch of one on the tiers of dhqr_solve_batched_c64
+  if (small_zfit(c, m, n)) return solve_batched(c, A, m, n, lda, 0, al, 0, b, 0, 1);
   // b carried in double-double (dhqr_complex.h, "the solve with b carried in double-double"): with the plain-double solve
   // the reference's acceptance statistic scored like the reference itself, up to 14 x LAPACK (round 4), so that path is gone
   CHECK(ensure(c, c->zsolve_lo, (size_t)(2 * m + 16)));
@@ -2472,6 +2523,28 @@ int32_t dhqr_ldiv_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
   if (no_columns(m, n)) return DHQR_OK;
   CHECK(check_mat(hA, m, n, lda, true));
   if (!halpha || !hb || !hx) return set_err(DHQR_EINVAL, "null pointer argument");
+  if (small_zfit(c, m, n)) {  // (the form of zqr_host_small; pinned: A | alpha | b | x)
+    const size_t na = (size_t)m * (size_t)n;
+    CHECK(small_pin_ensure(c, 2 * (na + 2 * (size_t)n + (size_t)m)));
+    double2 *pA = reinterpret_cast<double2 *>(c->small_pin), *pal = pA + na, *pb = pal + n, *px = pb + m;
+    unsigned long long *done = reinterpret_cast<unsigned long long *>(c->small_pin + c->small_pin_cap);
+    copy_cols(c->small_pin, 2 * m, hA, 2 * lda, 2 * m, n);
+    memcpy(pal, halpha, (size_t)n * sizeof(double2));
+    memcpy(pb, hb, (size_t)m * sizeof(double2));  // src:318 copy of b
+    if (batched_wave_fit(c, m, n)) {
+      CHECK(solve_batched(c, pA, m, n, m, 0, pal, 0, pb, 0, 1));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      memcpy(hx, pb, (size_t)n * sizeof(double2));  // src:320
+      return DHQR_OK;
+    }
+    // the kernel first brings the factor from the pinned buffer into device memory (its chunk pipeline would otherwise pay
+    // a PCIe round trip per chunk)
+    CHECK(ensure(c, c->small_dev, (size_t)SML_LDR * SML_LDR));
+    CHECK(small_zldiv(c, pA, m, m, n, pal, pb, pb, px, reinterpret_cast<double2 *>(c->small_dev.p), done, ++c->small_epoch, SmallBatch()));
+    CHECK(small_wait_done(c, done, c->small_epoch));
+    memcpy(hx, px, (size_t)n * sizeof(double2));  // src:320
+    return DHQR_OK;
+  }
   double *dA = nullptr, *dal = nullptr, *db = nullptr;
   const size_t esz = 2 * sizeof(double);
   if (hipMalloc((void **)&dA, (size_t)m * n * esz) != hipSuccess) return set_err(DHQR_ENOMEM, "hipMalloc failed");
@@ -2498,11 +2571,6 @@ int32_t dhqr_ldiv_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
 // The argument rules are those of the Float64 batched family (check_batched), in complex elements; nb: 0 or DHQR_ZNB; device
 // pointers are 16-byte aligned.  Tiers and host forms: dhqr_batched_host.h; kernels: dhqr_batched_complex.h,
 // dhqr_batched_complex_nrhs.h.
-static int32_t check_znb(int32_t nb) {
-  if (nb != 0 && nb != DHQR_ZNB)
-    return set_err(DHQR_EINVAL, "ComplexF64: nb must be 0 (unblocked) or %d (blocked); got %d", DHQR_ZNB, nb);
-  return DHQR_OK;
-}
 
 int32_t dhqr_factor_batched_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
                                 int64_t stride_alpha, int64_t batch, int32_t nb) {

@@ -8,8 +8,8 @@
 // route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single matrix is a batch of 1) --, everything else
 // PROMOTED: widened into a Float64 workspace of the context, the Float64 route with the caller's nb, rounded back.
 // ComplexF64 (dhqr_factor_batched_c64 ... dhqr_ldiv_batched_c64): the wave tier -- one launch of the kernels of
-// dhqr_batched_complex.h -- | a host loop over dhqr_factor_c64_nb / dhqr_solve_c64; the host forms are those of the real types
-// with T = double2.  Several right-hand sides, Q application, explicit Q and R (dhqr_solve_batched_nrhs_c64 ...
+// dhqr_batched_complex.h -- | up to 128 rows one launch of the single-workgroup kernels of dhqr_small_complex.h with grid =
+// batch | a host loop over dhqr_factor_c64_nb / dhqr_solve_c64; the host forms are those of the real types with T = double2.  Several right-hand sides, Q application, explicit Q and R (dhqr_solve_batched_nrhs_c64 ...
 // dhqr_form_r_batched_c64): the wave tier -- one launch of the kernels of dhqr_batched_complex_nrhs.h -- | the solve column
 // by column on the single-column route, Q on k_batched_zapplyq_general.
 // The host forms (qr_host, ldiv_host) end alike: after a failure of any step they still reach the final
@@ -18,6 +18,7 @@
 #pragma once
 #include <type_traits>
 #include "dhqr_batched_complex_nrhs.h"
+#include "dhqr_small_complex.h"
 
 static int32_t pipe_error_check(dhqr_ctx *c);  // (dhqr_api.hip, below this file's inclusion)
 
@@ -420,11 +421,42 @@ static int32_t form_r_batched(dhqr_ctx *c, const T *dA, int64_t n, int64_t lda, 
   return DHQR_OK;
 }
 
-// ---- ComplexF64 on the device: the wave tier, else matrix after matrix ---------------------------------------------------
-// (lda and the strides count complex elements; nb was checked by the caller: 0 or DHQR_ZNB, ignored on the wave tier)
+// ---- ComplexF64 on the device: the wave tier | one workgroup per matrix | matrix after matrix ------------------------------
+// The one-workgroup tier (dhqr_small_complex.h): ONE shape rule for single and batched calls alike.  The single-matrix
+// entry points (dhqr_factor_c64 ... dhqr_ldiv_c64) call factor_batched / solve_batched below with a batch of one whenever
+// it holds, so a single call and a batch of one are the same launch.
+static inline bool small_zfit(const dhqr_ctx *c, int64_t m, int64_t n) { return c->small_route && n >= 1 && n <= m && m <= SMZ_MAX; }
+// One launch of k_small_zqr, one n_rank1 group whatever the batch.  done != nullptr: a host-array call on the pinned
+// staging buffer (small_signal_done).
+static int32_t small_zqr(dhqr_ctx *c, const double2 *Asrc, int64_t lds, double2 *Adst, int64_t ldd, int64_t m, int64_t n, double2 *alpha,
+                         unsigned long long *done, unsigned long long epoch, const SmallBatch &sb) {
+  CHECK(prof_begin(c, CAT_RANK1));
+  hipLaunchKernelGGL(k_small_zqr, dim3((unsigned)sb.batch), dim3(SMZ_THREADS), 0, c->stream, Asrc, lds, Adst, ldd, (int)m, (int)n, alpha,
+                     done, epoch, sb.strideA, sb.strideA, sb.stride_alpha);
+  LAUNCHCHECK();
+  if (c->profiling)  // (as the wave tier counts: an element update reads and writes one complex element)
+    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)sb.batch * 32.0 * (double)(m - j) * (double)(n - j - 1);
+  return prof_end(c);
+}
+// One launch of k_small_zldiv, one n_solve whatever the batch.  Awork: device memory for a factor that lies in pinned host
+// memory (else nullptr).
+static int32_t small_zldiv(dhqr_ctx *c, const double2 *A, int64_t lda, int64_t m, int64_t n, const double2 *alpha, const double2 *bin,
+                           double2 *bout, double2 *xout, double2 *Awork, unsigned long long *done, unsigned long long epoch,
+                           const SmallBatch &sb) {
+  CHECK(prof_begin(c, CAT_SOLVE));
+  hipLaunchKernelGGL(k_small_zldiv, dim3((unsigned)sb.batch), dim3(SML_THREADS), 0, c->stream, A, lda, (int)m, (int)n, alpha, bin, bout,
+                     xout, Awork, done, epoch, sb.strideA, sb.stride_alpha, sb.strideb);
+  LAUNCHCHECK();
+  return prof_end(c);
+}
+
+// (lda and the strides count complex elements; nb was checked by the caller: 0 or DHQR_ZNB, ignored on the first two tiers)
 static int32_t factor_batched(dhqr_ctx *c, double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double2 *dalpha,
                               int64_t stride_alpha, int64_t batch, int32_t nb, bool /*single*/ = false) {
-  if (!batched_wave_fit(c, m, n)) {  // serial: that call's bits and profiling counts, synchronised after each (see Float64)
+  const bool wave = batched_wave_fit(c, m, n);
+  if (!wave && small_zfit(c, m, n))  // workgroup k on matrix k: asynchronous, one launch
+    return small_zqr(c, dA, lda, dA, lda, m, n, dalpha, nullptr, 0, SmallBatch{batch, strideA, stride_alpha});
+  if (!wave) {  // serial: that call's bits and profiling counts, synchronised after each (see Float64)
     for (int64_t k = 0; k < batch; ++k) {
       CHECK(dhqr_factor_c64_nb(c, reinterpret_cast<double *>(dA + k * strideA), m, n, lda,
                                reinterpret_cast<double *>(dalpha + k * stride_alpha), nb));
@@ -443,7 +475,10 @@ static int32_t factor_batched(dhqr_ctx *c, double2 *dA, int64_t m, int64_t n, in
 
 static int32_t solve_batched(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double2 *dalpha,
                              int64_t stride_alpha, double2 *db, int64_t strideb, int64_t batch, bool /*single*/ = false) {
-  if (!batched_wave_fit(c, m, n)) {
+  const bool wave = batched_wave_fit(c, m, n);
+  if (!wave && small_zfit(c, m, n))  // (the factor is in device memory: no Awork)
+    return small_zldiv(c, dA, lda, m, n, dalpha, db, db, nullptr, nullptr, nullptr, 0, SmallBatch{batch, strideA, stride_alpha, strideb});
+  if (!wave) {
     for (int64_t k = 0; k < batch; ++k) {
       CHECK(dhqr_solve_c64(c, reinterpret_cast<const double *>(dA + k * strideA), m, n, lda,
                            reinterpret_cast<const double *>(dalpha + k * stride_alpha), reinterpret_cast<double *>(db + k * strideb)));

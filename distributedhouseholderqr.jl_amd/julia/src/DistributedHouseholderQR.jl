@@ -193,6 +193,8 @@ end
 # ---- ComplexF64 methods ------------------------------------------------------------------------
 # nb = 64 (default for n >= 256): panels of 64 complex reflectors, trailing update on the FP64 MFMA kernels through the
 # real 2 x 2 embedding; nb = 0: the reference's unblocked order (src:171-196).  Same factorisation either way.
+# Up to 128 rows (the reference's first test shape, 110 x 100) qr! and \ are ONE single-workgroup launch each on the
+# library's pinned staging buffer, whatever nb (dhqr.h, the ComplexF64 section).
 const DHQR_ZNB = 64
 function householder!(A::StridedMatrix{ComplexF64}, α::Vector{ComplexF64}; nb::Integer=(size(A, 2) >= 256 ? DHQR_ZNB : 0))
   (nb == 0 || nb == DHQR_ZNB) || throw(ArgumentError("ComplexF64: nb must be 0 (unblocked) or $(DHQR_ZNB) (blocked)"))

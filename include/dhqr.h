@@ -39,7 +39,8 @@ extern "C" {
                           * dhqr_qr_batched_f32, dhqr_ldiv_batched_f32;
                           * dhqr_solve_batched_nrhs_f64, dhqr_ldiv_batched_nrhs_f64, dhqr_solve_batched_nrhs_f32,
                           * dhqr_ldiv_batched_nrhs_f32;
-                          * dhqr_factor_batched_c64, dhqr_solve_batched_c64, dhqr_qr_batched_c64, dhqr_ldiv_batched_c64 */
+                          * dhqr_factor_batched_c64, dhqr_solve_batched_c64, dhqr_qr_batched_c64, dhqr_ldiv_batched_c64;
+                          * the one-workgroup ComplexF64 route up to 128 rows behind the existing dhqr_*_c64 names (no new symbol) */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -132,7 +133,11 @@ int32_t dhqr_get_tsqr_count(dhqr_ctx *ctx, int64_t *n_tsqr);
  * Above 128 rows the kernel's waves hand columns and reflectors to each other through LDS flags instead of a barrier per
  * column; those waits are bounded, and a kernel that gave up on one answers NaN in every alpha (never a hung device):
  * dhqr_qr_f64 then factors once more with the barrier form by itself; a caller of the device-resident, asynchronous
- * dhqr_factor_f64 sees the NaN (DHQR_TUNE small_flags=0 selects the barrier form from the start). */
+ * dhqr_factor_f64 sees the NaN (DHQR_TUNE small_flags=0 selects the barrier form from the start).
+ * ComplexF64: 1 <= n <= m <= 128 take ONE launch per qr! and per `\` too (dhqr_factor_c64, dhqr_factor_c64_nb, dhqr_solve_c64,
+ * and dhqr_qr_c64 / dhqr_qr_c64_nb / dhqr_ldiv_c64 on the pinned staging buffer; csrc/dhqr_small_complex.h), in the barrier
+ * form only: that kernel waits on nothing but a workgroup barrier and has no NaN answer of this kind.  on = 0: today's general
+ * ComplexF64 routes for every shape. */
 int32_t dhqr_set_small_route(dhqr_ctx *ctx, int32_t on);
 /* Solves this context REPEATED with one launch per panel step because a wait of the persistent Q'b kernel (all of whose
  * workgroups must be resident at once) expired -- another process or stream held compute units.  The repetition happens
@@ -416,7 +421,21 @@ int32_t dhqr_partialdot_host_f64(dhqr_ctx *ctx, const double *ha, const double *
  * dhqr_factor_c64_nb / dhqr_qr_c64_nb: the same with a panel width: nb = 0 unblocked, nb = DHQR_ZNB (64 complex columns)
  *                   BLOCKED: the panel's block reflector I - V T V^H is applied to the trailing matrix by the Float64
  *                   MFMA kernels through the real 2 x 2 embedding of the 64 complex reflectors (= 128 real columns);
- *                   identical factor format and values (to rounding). */
+ *                   identical factor format and values (to rounding).
+ *
+ * The one-workgroup route (small route on, 1 <= n <= m <= 128; csrc/dhqr_small_complex.h): the matrix -- at most 256 KB --
+ * lives in the registers of one compute unit as (re, im) and the reference's column-by-column algorithm runs as written, one
+ * workgroup barrier per column; the solve carries both parts of b in double-double and divides by alpha_j as the general
+ * solve does.  dhqr_factor_c64, dhqr_factor_c64_nb (whatever nb says; another nb than 0 or DHQR_ZNB is still DHQR_EINVAL) and
+ * dhqr_solve_c64 make ONE asynchronous launch on the ctx stream: the batched tiers below on a batch of one (the wave kernel
+ * up to 64 x 32, the workgroup kernel beyond), so a single call has the bits of dhqr_factor_batched_c64 /
+ * dhqr_solve_batched_c64 with batch = 1, whatever lda.  dhqr_qr_c64, dhqr_qr_c64_nb and dhqr_ldiv_c64 copy into the context's
+ * pinned staging buffer, make that one launch on it and copy out: no hipMalloc, hipFree or hipMemcpy, the bits of the
+ * device-resident call; dhqr_trim releases the buffer.  Only these entry points: the panels of the blocked driver and of the
+ * column-split and multi-GPU drivers keep their kernels whatever their size.  With profiling on a factor counts ONE n_rank1
+ * group and a solve one n_solve.  A column whose reflector is not finite leaves what the reference leaves (finite columns
+ * in front, alpha as formed there, NaN from that row on in the columns from there on).
+ * Measured boundary: profiles/small_c64.txt. */
 #define DHQR_ZNB 64
 int32_t dhqr_factor_c64_nb(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, double *dalpha, int32_t nb);
 int32_t dhqr_qr_c64_nb(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, double *halpha, int32_t nb);
@@ -444,10 +463,15 @@ int32_t dhqr_partialdot_host_c64(dhqr_ctx *ctx, const double *ha, const double *
  *                            solve carries both parts of b in double-double and divides by alpha_j as dhqr_solve_c64 does.
  *                            Asynchronous on the ctx stream.  nb is ignored.  With profiling on a factor counts ONE n_rank1
  *                            group and a solve one n_solve, whatever the batch.
+ *   otherwise m <= 128       (small route on) ONE launch of the single-workgroup kernels of the ComplexF64 section above
+ *                            (csrc/dhqr_small_complex.h) with grid = batch, workgroup k on matrix k: the bits of
+ *                            dhqr_factor_c64 / dhqr_solve_c64 on matrix k alone, independent of lda, the strides, the batch
+ *                            and the position in it.  Asynchronous on the ctx stream.  nb is ignored.  ONE n_rank1 group
+ *                            per factor and one n_solve per solve, whatever the batch.
  *   everything else, and every shape when the small route is off (dhqr_set_small_route(ctx, 0), DHQR_SMALL=0)
  *                            a host loop over dhqr_factor_c64_nb (with the caller's nb) / dhqr_solve_c64 on matrix k alone:
  *                            serial, synchronised after every matrix; that call's bits and its profiling counts.
- *                            Synchronous.  (A one-workgroup tier like the Float64 one does not exist for ComplexF64.)
+ *                            Synchronous.
  *   dhqr_qr_batched_c64, dhqr_ldiv_batched_c64
  *                            host in / host out, synchronous; staged through the context's device copy of a batch (the one
  *                            dhqr_qr_batched_f64 uses; dhqr_trim releases it).  On an error return hA is undefined; hb is not

@@ -422,7 +422,7 @@ def main():
              f"# batched = one dhqr_factor_batched_{t} + one dhqr_solve_batched_{t}; looped = batch x (dhqr_factor_{t} + dhqr_solve_{t}), small route on",
              "# one-CU = the batched calls with DHQR_TUNE batched_wave=0 (one workgroup per matrix) on the wave tier's shapes"]
     if t == "c64":
-        lines[2] = "# (ComplexF64 has no one-workgroup tier: no one-CU column)"
+        lines[2] = "# (ComplexF64: one wave per matrix up to 64 x 32, one workgroup per matrix up to 128 rows; no one-CU column is measured)"
     print("\n".join(lines), flush=True)
     for (m, n) in shapes:
         for batch in batches:
