@@ -882,7 +882,10 @@ def solve_batched_nrhs(H: DistributedHouseholderQRStruct, B):
     with a single one -> X (batch, n, nrhs) / (n, nrhs), column-major.  B is NOT modified.  complex128:
     dhqr_solve_batched_nrhs_c64 on a copy of a device B (its matrices column-major like the factor's),
     dhqr_ldiv_batched_nrhs_c64 on numpy arrays (any layout; copied where the layout asks for it); column r of X has the bits
-    of ldiv_batched on the vectors B[..., r].  float64 / float32: ldiv(H, B)."""
+    of ldiv_batched on the vectors B[..., r].  Up to 64 x 32 one wave per matrix; beyond that, up to 128 rows, one launch of the
+    one-workgroup multi-column kernel (a workgroup per matrix and group of 6 columns) where that was measured to beat the column
+    loop (2 .. 6 and 13 .. 18 columns; the same bits either way).  float64 / float32:
+    ldiv(H, B)."""
     A, α = H.A, H.α
     _same_field(A, B, "B")
     _same_field(A, α, "α")
@@ -928,7 +931,9 @@ def solve_batched_nrhs(H: DistributedHouseholderQRStruct, B):
 def apply_q_batched_(H: DistributedHouseholderQRStruct, B, trans: bool):
     """B <- Q^H B (trans) or Q B, in place, device tensors only, every element type: complex128 through
     dhqr_apply_q_batched_c64 (a (batch, m, n) factor with B (batch, m, nrhs), or one matrix with B (m, nrhs), matrices
-    column-major); float64 / float32: apply_q_(H, B, trans)."""
+    column-major) -- up to 128 rows one launch that carries every column in double-double, so rows n .. m-1 of Q^H B have the
+    bits of what solve_batched_nrhs leaves there and a column's bits do not depend on its neighbours; float64 / float32:
+    apply_q_(H, B, trans)."""
     A = H.A
     _same_field(A, B, "B")
     if not _is_complex(A):
@@ -944,7 +949,8 @@ def apply_q_batched_(H: DistributedHouseholderQRStruct, B, trans: bool):
 
 def form_q_batched(H: DistributedHouseholderQRStruct):
     """explicit thin Q of a device factorisation of every element type: (batch, m, n) for a batch, (m, n) for one matrix,
-    column-major.  complex128: dhqr_form_q_batched_c64; float64 / float32: get_q(H)."""
+    column-major.  complex128: dhqr_form_q_batched_c64 (up to 128 rows one launch, equal to apply_q_batched_(H, [I; 0], False) for
+    a finite factor); float64 / float32: get_q(H)."""
     A = H.A
     if not _is_complex(A):
         return get_q(H)

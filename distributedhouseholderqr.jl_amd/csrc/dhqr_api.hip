@@ -1349,6 +1349,7 @@ int32_t dhqr_create(dhqr_ctx **out, int32_t device) {
     { long long v; if (tune_get("small_flags", &v)) c->small_flags = v != 0; }
     { long long v; if (tune_get("batched_wave", &v)) c->batched_wave = v != 0; }
     { long long v; if (tune_get("znrhs_wave", &v)) c->znrhs_wave = v < 0 ? -1 : (v != 0); }
+    { long long v; if (tune_get("zsmall_nrhs", &v)) c->zsmall_nrhs = v < 0 ? -1 : (v != 0); }
     { long long v; if (tune_get("short_panel_small", &v)) c->short_panel_small = v != 0; }
     { long long v; if (tune_get("partial_unblocked", &v)) c->partial_unblocked = v != 0; }
     { long long v; if (tune_get("partial_unblocked_max_rows", &v)) c->partial_unblocked_max_rows = v; }

@@ -10,8 +10,10 @@
 // ComplexF64 (dhqr_factor_batched_c64 ... dhqr_ldiv_batched_c64): the wave tier -- one launch of the kernels of
 // dhqr_batched_complex.h -- | up to 128 rows one launch of the single-workgroup kernels of dhqr_small_complex.h with grid =
 // batch | a host loop over dhqr_factor_c64_nb / dhqr_solve_c64; the host forms are those of the real types with T = double2.  Several right-hand sides, Q application, explicit Q and R (dhqr_solve_batched_nrhs_c64 ...
-// dhqr_form_r_batched_c64): the wave tier -- one launch of the kernels of dhqr_batched_complex_nrhs.h -- | the solve column
-// by column on the single-column route, Q on k_batched_zapplyq_general.
+// dhqr_form_r_batched_c64): the wave tier -- one launch of the kernels of dhqr_batched_complex_nrhs.h -- | up to 128 rows
+// one launch of k_small_zapply (dhqr_small_complex_nrhs.h), a workgroup per (matrix, group of SMZA_CW columns of B): Q and
+// the explicit Q for every nrhs, the solve where that was measured to pay (zsmall_nrhs_pays: one or three groups of columns)
+// | the solve column by column on the single-column route (the same bits), Q on k_batched_zapplyq_general.
 // The host forms (qr_host, ldiv_host) end alike: after a failure of any step they still reach the final
 // hipStreamSynchronize -- nothing is left in flight on the caller's arrays -- and return the FIRST error.  (Before, the
 // single-column ldiv forms returned from a failed enqueue of the copy of X without it.)
@@ -19,6 +21,7 @@
 #include <type_traits>
 #include "dhqr_batched_complex_nrhs.h"
 #include "dhqr_small_complex.h"
+#include "dhqr_small_complex_nrhs.h"
 
 static int32_t pipe_error_check(dhqr_ctx *c);  // (dhqr_api.hip, below this file's inclusion)
 
@@ -367,6 +370,32 @@ static int32_t solve_batched_nrhs(dhqr_ctx *c, const float *dA, int64_t m, int64
   });
 }
 
+// ---- ComplexF64 beyond the wave tier, up to 128 rows: one workgroup per (matrix, group of columns of B) --------------------
+static inline bool small_zfit(const dhqr_ctx *c, int64_t m, int64_t n);  // (the one-workgroup tier's shape rule, below)
+static inline bool small_znrhs_fit(const dhqr_ctx *c, int64_t m, int64_t n) { return !batched_wave_fit(c, m, n) && small_zfit(c, m, n); }
+static inline int64_t small_zapply_groups(int64_t nrhs) { return (nrhs + SMZA_CW - 1) / SMZA_CW; }
+// ONE launch of k_small_zapply<mode> on a 1-D grid of batch * groups (the caller has checked that it fits), one n_solve
+// group whatever nrhs and batch.  dalpha: SMZA_SOLVE alone (else nullptr).
+static int32_t small_zapply(dhqr_ctx *c, int mode, const double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                            const double2 *dalpha, int64_t stride_alpha, double2 *dB, int64_t nrhs, int64_t ldb, int64_t strideB,
+                            int64_t batch) {
+  CHECK(prof_begin(c, CAT_SOLVE));
+  const int64_t groups = small_zapply_groups(nrhs);
+  const dim3 grid((unsigned)(batch * groups)), block(SMZA_THREADS);
+#define SMZA_LAUNCH(mode_)                                                                                                        \
+  hipLaunchKernelGGL(k_small_zapply<mode_>, grid, block, 0, c->stream, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, \
+                     (int)nrhs, ldb, strideB, (int)groups)
+  switch (mode) {
+    case SMZA_SOLVE: SMZA_LAUNCH(SMZA_SOLVE); break;
+    case SMZA_QH: SMZA_LAUNCH(SMZA_QH); break;
+    case SMZA_QN: SMZA_LAUNCH(SMZA_QN); break;
+    default: SMZA_LAUNCH(SMZA_FORMQ);
+  }
+#undef SMZA_LAUNCH
+  LAUNCHCHECK();
+  return prof_end(c);
+}
+
 // ---- Q application, explicit Q and R (dhqr.h: dhqr_apply_q_batched_f64 ...) -----------------------------------------------
 // The wave tier: one launch.  Every other shape, Float64: matrix after matrix on apply_q_impl, the blocked route of
 // dhqr_apply_q_f64 (its bits) -- the explicit Q from [I; 0] --, all of it enqueued on the stream; Float32: PROMOTED.
@@ -375,9 +404,18 @@ static int32_t apply_q_batched(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, i
                                int64_t ldb, int64_t strideB, int64_t batch, int trans, bool formq) {
   if (batched_wave_fit(c, m, n)) return wave_apply_q(c, dA, m, n, lda, strideA, dB, nrhs, ldb, strideB, batch, trans, formq);
   if constexpr (std::is_same_v<T, double2>) {
-    // ComplexF64 has no blocked apply-Q: [I; 0] for the explicit Q, then ONE launch of the plain kernel, a workgroup per
-    // (matrix, column of B) on a 1-D grid (batch * nrhs may exceed a y dimension)
+    // ComplexF64 has no blocked apply-Q.  Beyond 128 rows and with the small route off: [I; 0] for the explicit Q, then ONE
+    // launch of the plain kernel, a workgroup per (matrix, column of B) on a 1-D grid (batch * nrhs may exceed a y dimension)
     if (batch * nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch * nrhs = %lld too large", (long long)(batch * nrhs));
+    // Up to 128 rows: the one-workgroup kernel, which reads the factor once per SMZA_CW columns and carries a column in
+    // double-double as every other ComplexF64 kernel of the family does.  By SHAPE alone, never by nrhs or batch: the two
+    // kernels round differently, and a column's bits may not depend on its neighbours.  Measured, batch 16384
+    // (profiles/small_c64_nrhs_throughput.txt): the explicit Q is 1.46 - 1.71 x the general kernel; Q^H B and Q B are NOT
+    // faster -- 0.81 - 0.91 x at 66 x 33 in every round, 0.97 - 1.02 x at 110 x 100 and 128 x 128 -- and take this kernel for
+    // the contracts above, which the general kernel cannot give.  (DHQR_TUNE zsmall_nrhs=0: the general kernel.)
+    if (small_znrhs_fit(c, m, n) && c->zsmall_nrhs != 0)
+      return small_zapply(c, formq ? SMZA_FORMQ : trans ? SMZA_QH : SMZA_QN, dA, m, n, lda, strideA, nullptr, 0, dB, nrhs, ldb, strideB,
+                          batch);
     if (formq) {
       const int64_t total = m * nrhs * batch;
       hipLaunchKernelGGL(k_batched_eye<double2>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32)), dim3(256), 0, c->stream,
@@ -503,13 +541,33 @@ static int32_t solve_batched(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t 
 // (DHQR_TUNE znrhs_wave=1 / 0: always the kernel / the loop, for measurements and for the tests of the tail groups.)
 static inline bool znrhs_wave_pays(int64_t nrhs, int64_t n) { return nrhs >= 4 && nrhs % BQZN_RG(wave_nc(n)) == 0; }
 
-// The wave tier where it pays: the multi-column kernel.  Every other call: the single-column route, column by column -- its
-// tiers, its synchronisation, its profiling counts, its bits (a column of complex elements stays 16-byte aligned).
+// Does the one-workgroup multi-column kernel (k_small_zapply<SMZA_SOLVE>) pay against the loop of nrhs k_small_zldiv launches?
+// Measured on the MI355X (profiles/small_c64_nrhs_throughput.txt: batch 16384, resident factor, 66 x 33 / 110 x 100 /
+// 128 x 128, K = 2, 4, 8, 16 columns, one process per arm -- DHQR_TUNE zsmall_nrhs=1 against zsmall_nrhs=0 --, five rounds
+// of ten repetitions, round by round; ratios move by up to 3 % from round to round).  ONE group of SMZA_CW = 6 columns wins
+// in every round: K = 2 1.05 - 1.09 x, K = 4 1.56 - 1.67 x.  THREE groups (K = 16: 6 + 6 + 4) win in every round: 1.34 -
+// 1.47 x; a batch of one at 110 x 100 with 16 columns takes 202 us instead of 1815 us.  TWO groups (K = 8: 6 + 2) LOSE in
+// every round at every shape, 0.81 - 0.92 x: the second launch-worth of workgroups costs more than its columns' share,
+// which the measurement shows and does not explain.  No other number of groups was measured.  So: the kernel for 2 .. 6 and
+// for 13 .. 18 columns, the column loop -- the same bits -- for every other call.
+// (DHQR_TUNE zsmall_nrhs=1 / 0: always the kernel / always the routes without it, for measurements and tests.)
+static inline bool zsmall_nrhs_pays(int64_t nrhs) {
+  const int64_t groups = small_zapply_groups(nrhs);
+  return nrhs >= 2 && (groups == 1 || groups == 3);
+}
+
+// The wave tier and the one-workgroup tier where they pay: their multi-column kernels.  Every other call: the single-column
+// route, column by column -- its tiers, its synchronisation, its profiling counts, its bits (a column of complex elements
+// stays 16-byte aligned).
 static int32_t solve_batched_nrhs(dhqr_ctx *c, const double2 *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                   const double2 *dalpha, int64_t stride_alpha, double2 *dB, int64_t nrhs, int64_t ldb, int64_t strideB,
                                   int64_t batch) {
   if (batched_wave_fit(c, m, n) && (c->znrhs_wave < 0 ? znrhs_wave_pays(nrhs, n) : c->znrhs_wave != 0))
     return wave_solve_nrhs(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
+  // (a grid of batch * groups workgroups that does not fit a launch: the column loop, the same bits)
+  if (small_znrhs_fit(c, m, n) && (c->zsmall_nrhs < 0 ? zsmall_nrhs_pays(nrhs) : c->zsmall_nrhs != 0) &&
+      batch * small_zapply_groups(nrhs) <= 0x7fffffffLL)
+    return small_zapply(c, SMZA_SOLVE, dA, m, n, lda, strideA, dalpha, stride_alpha, dB, nrhs, ldb, strideB, batch);
   for (int64_t r = 0; r < nrhs; ++r)
     CHECK(solve_batched(c, dA, m, n, lda, strideA, dalpha, stride_alpha, dB + r * ldb, strideB, batch));
   return DHQR_OK;

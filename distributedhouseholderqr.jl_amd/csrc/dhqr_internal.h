@@ -144,6 +144,7 @@ struct dhqr_ctx {
   Buf f32_dev;                  // device staging of the Float32 host forms (floats, two per element of the Buf)
   int batched_wave = 1;         // batches of matrices of at most 64 x 32: one wave per matrix (dhqr_batched.h; DHQR_TUNE batched_wave=0: the one-CU kernels)
   int znrhs_wave = -1;          // ComplexF64 H \ B, several right-hand sides, wave tier: -1 the speed rule (dhqr_batched_host.h: znrhs_wave_pays), 0 always the column loop, 1 always the multi-column kernel (DHQR_TUNE znrhs_wave=: measurements)
+  int zsmall_nrhs = -1;         // ComplexF64 H \ B, apply-Q and explicit Q beyond the wave tier up to 128 rows: -1 the rule (dhqr_batched_host.h: k_small_zapply for Q at every nrhs, zsmall_nrhs_pays for the solve), 0 never the kernel (the column loop, k_batched_zapplyq_general), 1 always the kernel (DHQR_TUNE zsmall_nrhs=: measurements)
   bool coop = false;     // the device runs cooperative (all-resident) launches: false on the CPU emulator
   Buf host_mat;          // device copy of the caller's HOST matrix (+ alpha) of dhqr_qr_f64, kept between calls
   int pair = 1;                  // 1: wide updates apply two panels per pass (DHQR_PAIR=0 disables)

@@ -502,18 +502,30 @@ int32_t dhqr_ldiv_batched_c64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_
  *                            (small route on): ONE launch of the multi-column kernel (csrc/dhqr_batched_complex_nrhs.h: the
  *                            factor and alpha in registers once, the columns in groups of 1 / 2 / 4 for n <= 8 / 16 / 32)
  *                            where that was measured to beat the column loop -- nrhs >= 4 in full groups: 1.04 - 1.15 x,
- *                            profiles/batched_c64_nrhs_throughput.txt --, else, and at every other shape,
- *                            dhqr_solve_batched_c64 column by column: its tiers, synchronisation and counts.
+ *                            profiles/batched_c64_nrhs_throughput.txt --, else dhqr_solve_batched_c64 column by column.
+ *                            Beyond that, up to 128 rows (small route on): ONE launch of the one-workgroup multi-column
+ *                            kernel (csrc/dhqr_small_complex_nrhs.h: a workgroup per matrix and group of 6 columns, which
+ *                            reads the factor once for the group), one n_solve group whatever nrhs and batch, where that
+ *                            was measured to beat the column loop -- 2 .. 6 columns 1.05 - 1.67 x, 13 .. 18 columns 1.34 -
+ *                            1.47 x; two groups (7 .. 12 columns) lose: profiles/small_c64_nrhs_throughput.txt; DHQR_TUNE
+ *                            zsmall_nrhs=1 / 0: always / never.
+ *                            Every other call: dhqr_solve_batched_c64 column by column: its tiers, synchronisation and
+ *                            counts.
  *   dhqr_ldiv_batched_nrhs_c64   host in / host out through the staging area of dhqr_ldiv_batched_c64; hB is not modified
- *                            (src:318); X_k (n x nrhs) has the device form's bits.  Synchronous.
+ *                            (src:318); X_k (n x nrhs) has the device form's bits (and its tiers: the staged copy is device
+ *                            memory).  Synchronous.
  *   dhqr_apply_q_batched_c64 dB_k <- Q_k^H dB_k (trans = 1) or Q_k dB_k (trans = 0), in place; needs no alpha.
  *   dhqr_form_q_batched_c64  dQ_k (m x n, ldq) <- the explicit thin Q_k; nothing of dQ is read.
  *                            Both: m <= 64 and n <= 32 (small route on) ONE launch, one wave per matrix, a column carried in
  *                            double-double per component; rows n .. m-1 of trans = 1 have the bits of what the solve leaves
- *                            there; form_q compares equal to trans = 0 on [I; 0] for a finite factor.  Everything else, and
- *                            every shape with the small route off: ONE launch of a plain kernel, a workgroup per (matrix,
- *                            column), in place in device memory in plain double (form_q: [I; 0] first); it re-reads the
- *                            factor once per column -- a blocked ComplexF64 apply-Q for large matrices does not exist yet.
+ *                            there; form_q compares equal to trans = 0 on [I; 0] for a finite factor.  Beyond that, up to
+ *                            128 rows (small route on): ONE launch of the one-workgroup multi-column kernel
+ *                            (csrc/dhqr_small_complex_nrhs.h) for every nrhs and batch, with the same three properties and
+ *                            every column's bits independent of nrhs, of its place and of the batch (DHQR_TUNE
+ *                            zsmall_nrhs=0: the plain kernel below).  More than 128 rows, and every shape with the small
+ *                            route off: ONE launch of a plain kernel, a workgroup per (matrix, column), in place in device
+ *                            memory in plain double (form_q: [I; 0] first); it re-reads the factor once per column -- a
+ *                            blocked ComplexF64 apply-Q for large matrices does not exist yet.
  *                            Asynchronous on the ctx stream; with profiling on each launch counts one n_solve group.
  *   dhqr_form_r_batched_c64  dR_k (n x n, ldr) <- the strict upper part of H_k, alpha_k on the diagonal, zeros below: one
  *                            element-wise launch for every shape.  Asynchronous.

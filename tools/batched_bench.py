@@ -13,6 +13,12 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
                                                            (DHQR_TUNE znrhs_wave=1) against the loop of K
                                                            dhqr_solve_batched_c64 calls, and the library's own rule, ROUNDS
                                                            rounds each.  With --applyq: as for the real types
+                                                           Shapes beyond the wave tier up to 128 rows (e.g. --shapes
+                                                           66x33,110x100,128x128) with --nrhs K or --applyq: the one-workgroup
+                                                           multi-column kernel (DHQR_TUNE zsmall_nrhs=1) against the routes
+                                                           without it (zsmall_nrhs=0: the column loop, the general apply-Q
+                                                           kernel), one child process per arm in the same environment, ROUNDS
+                                                           rounds each, kernel / parent round by round
        --shapes 16x8,32x16                                 only these shapes (default: every shape of SHAPES)
        --nrhs K [--batches 16384]                          `H_k \\ B_k` with K right-hand sides per matrix instead: ONE
                                                            dhqr_solve_batched_nrhs_* call against the loop of K
@@ -304,6 +310,110 @@ def point_applyq(m, n, batch, nrhs, op, dtype="f64"):
     print("POINT " + json.dumps(out), flush=True)
 
 
+def small_tier(m, n):
+    """a ComplexF64 shape of the one-workgroup tier: beyond one wave per matrix, up to 128 rows"""
+    return (m > 64 or n > 32) and n <= m <= 128
+
+
+def point_arm(m, n, batch, nrhs, op):
+    """one arm of the one-workgroup ComplexF64 comparison (the parent process has set DHQR_TUNE zsmall_nrhs=1 or 0): op = s
+    (dhqr_solve_batched_nrhs_c64), t, n (dhqr_apply_q_batched_c64) or q (dhqr_form_q_batched_c64) on a resident factor, ROUNDS
+    rounds; `sum`: a checksum of the result's bits (the solve's two arms must agree on it)"""
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as g
+    pkg = g.import_package()
+    os.environ["DHQR_SMALL"] = "1"
+    cols = n if op == "q" else nrhs
+    A = pkg.rand_colmajor_batched_c(batch, m, n, 1, "cuda:0")
+    B0 = pkg.empty_colmajor_batched_c(batch, m, cols, "cuda:0")
+    if op == "q":
+        B0.zero_()
+    else:
+        for r in range(cols):
+            B0[:, :, r] = pkg.rand_colmajor_batched_c(batch, m, 1, 7 + 1000 * r, "cuda:0").reshape(batch, m)
+    B = B0.clone(memory_format=torch.preserve_format)
+    assert B.stride() == B0.stride() == (m * cols, 1, m)
+    H = pkg.qr_batched_(A)
+    torch.cuda.synchronize()
+    L = pkg._lib.lib()
+    P = ctypes.c_void_p
+    pa, pal, pb = A.data_ptr(), H.α.data_ptr(), B.data_ptr()
+
+    def call(h):
+        if op == "s":
+            pkg._lib.check(L.dhqr_solve_batched_nrhs_c64(h, P(pa), m, n, m, m * n, P(pal), n, P(pb), cols, m, m * cols, batch))
+        elif op == "q":
+            pkg._lib.check(L.dhqr_form_q_batched_c64(h, P(pa), m, n, m, m * n, P(pb), m, m * cols, batch))
+        else:
+            pkg._lib.check(L.dhqr_apply_q_batched_c64(h, P(pa), m, n, m, m * n, P(pb), cols, m, m * cols, batch, 1 if op == "t" else 0))
+
+    ctx = pkg.Context(0)
+    out = {"m": m, "n": n, "batch": batch, "nrhs": cols, "op": op, "tune": os.environ.get("DHQR_TUNE", ""), "rounds": []}
+    for _ in range(ROUNDS):
+        rates = []
+        for r in range(WARMUP + REPS):
+            B.copy_(B0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call(ctx.handle)
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(batch / dt)
+        out["rounds"].append({"median": statistics.median(rates), "min": min(rates), "max": max(rates)})
+    ctx.close()
+    out["sum"] = int(torch.view_as_real(B).contiguous().view(torch.int64).sum().item())
+    print("POINT " + json.dumps(out), flush=True)
+
+
+def main_arms(a, shapes, batches):
+    op, K = (a.applyq or "s"), (a.nrhs or 16)
+    what = {"s": f"H_k \\ B_k (dhqr_solve_batched_nrhs_c64), {K} right-hand sides", "t": f"B_k <- Q_k^H B_k (dhqr_apply_q_batched_c64), {K} columns",
+            "n": f"B_k <- Q_k B_k (dhqr_apply_q_batched_c64), {K} columns", "q": "explicit thin Q_k (dhqr_form_q_batched_c64, nrhs = n)"}[op]
+    lines = [f"# tools/batched_bench.py --dtype c64 {'--applyq ' + op if a.applyq else ''} --nrhs {K}: {what}, resident factor; matrices per second",
+             f"# kernel = DHQR_TUNE zsmall_nrhs=1 (k_small_zapply), parent = zsmall_nrhs=0 (" +
+             ("the loop of k_small_zldiv launches; the same bits, checked" if op == "s" else "k_batched_zapplyq_general") +
+             f"); one child process per arm; {ROUNDS} rounds of {REPS} repetitions each: every round's median, then min .. max over all repetitions"]
+    print("\n".join(lines), flush=True)
+    rounds = lambda rs: " ".join(f"{x['median']:.0f}" for x in rs) + f" ({min(x['min'] for x in rs):.0f} .. {max(x['max'] for x in rs):.0f})"
+    rc = 0
+    for (m, n) in shapes:
+        for batch in batches:
+            arms = {}
+            for arm in ("1", "0"):
+                env = dict(os.environ, DHQR_TUNE=f"zsmall_nrhs={arm}")
+                p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point", str(m), str(n),
+                                    str(batch), "--dtype", "c64", "--nrhs", str(K), "--arm", op], capture_output=True, text=True, env=env)
+                row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
+                if p.returncode != 0 or not row:
+                    lines.append(f"{m}x{n} batch {batch} {op} zsmall_nrhs={arm}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
+                    print(lines[-1], flush=True)
+                    rc = 1
+                    break
+                arms[arm] = json.loads(row[0][6:])
+            if rc:
+                break
+            k, o = arms["1"], arms["0"]
+            if op == "s" and k["sum"] != o["sum"]:
+                lines.append(f"{m}x{n} batch {batch}: the two arms of the solve differ in a bit; stopping")
+                print(lines[-1], flush=True)
+                rc = 1
+                break
+            ratios = [x["median"] / y["median"] for x, y in zip(k["rounds"], o["rounds"])]
+            med = lambda rs: statistics.median(x["median"] for x in rs)
+            txt = (f"{m:4d} x {n:<4d} batch {k['batch']:6d} nrhs {k['nrhs']:3d} c64 {op} | kernel {rounds(k['rounds'])} | parent {rounds(o['rounds'])} | "
+                   f"kernel/parent per round {' '.join(f'{x:.3f}' for x in ratios)} | median {med(k['rounds']) / med(o['rounds']):5.2f}x")
+            lines.append(txt)
+            print(txt, flush=True)
+        if rc:
+            break
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return rc
+
+
 def main_applyq(a, shapes, batches):
     t, K, op = a.dtype, (a.nrhs or 16), a.applyq
     what = {"t": "B_k <- Q_k'B_k", "n": "B_k <- Q_k B_k", "q": "explicit thin Q_k (nrhs = n)"}[op]
@@ -401,10 +511,13 @@ def main():
     ap.add_argument("--nrhs", type=int, default=None, help="right-hand sides per matrix: the multi-column solve against the column loop")
     ap.add_argument("--applyq", choices=("t", "n", "q"), default=None, help="Q'B, QB or the explicit Q of a resident batched factor")
     ap.add_argument("--batches", default=None, help="e.g. 16384 or 64,1024 (default: every batch of BATCHES)")
+    ap.add_argument("--arm", choices=("s", "t", "n", "q"), default=None, help="(what main_arms runs in a child: one arm of one point)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
     a = ap.parse_args()
     if a.point:
-        if a.applyq is not None:
+        if a.arm is not None:
+            point_arm(*a.point, a.nrhs or 16, a.arm)
+        elif a.applyq is not None:
             point_applyq(*a.point, a.nrhs or 16, a.applyq, a.dtype)
         elif a.nrhs is not None:
             point_nrhs(*a.point, a.nrhs, a.dtype)
@@ -414,6 +527,8 @@ def main():
     t = a.dtype
     shapes = (C64_SHAPES if t == "c64" else SHAPES) if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
     batches = (C64_BATCHES if t == "c64" else BATCHES) if a.batches is None else [int(v) for v in a.batches.split(",")]
+    if t == "c64" and (a.applyq is not None or a.nrhs is not None) and all(small_tier(m, n) for m, n in shapes):
+        return main_arms(a, shapes, batches if a.batches is not None else [16384])
     if a.applyq is not None:
         return main_applyq(a, shapes, batches if a.batches is not None else [16384])
     if a.nrhs is not None:
