@@ -174,10 +174,12 @@ static inline const int *pred_stat(dhqr_ctx *c) { return c->epoch >= 0 ? c->dsta
 // (k_gemm_nn_sub<..., TR = 64>): twice the workgroups, half the K-loop time each -- the lane's critical chain.
 template <int KW, bool INIT0 = false>
 static void launch_nn_sub(dhqr_ctx *c, bool vec, dim3 grid, const double *V, int64_t ldv, const double *W, int64_t ldw,
-                          double *C, int64_t ldc, int64_t rows, int64_t ncols, int swz, bool predicated) {
+                          double *C, int64_t ldc, int64_t rows, int64_t ncols, int swz, bool predicated, int64_t rows_all = -1) {
   const int *st = predicated ? pred_stat(c) : nullptr;
   const int64_t ntiles = (ncols + 127) / 128;
-  if (vec && !swz && ntiles <= 2 && ((rows + 127) / 128) * ntiles < 512) {
+  // rows_all: this launch is a ROW RANGE of an update of rows_all rows (the early top of the panel chain): the tile height
+  // is that of the whole update, so that every tile is the tile of the one-launch form, to the bit
+  if (vec && !swz && ntiles <= 2 && (((rows_all >= 0 ? rows_all : rows) + 127) / 128) * ntiles < 512) {
     const dim3 g64((unsigned)((rows + 63) / 64), (unsigned)ntiles);
     hipLaunchKernelGGL((k_gemm_nn_sub<2, KW, INIT0, false, 64>), g64, dim3(256), 0, c->stream, V, ldv, W, ldw, C, ldc, rows, ncols,
                        0, st, c->epoch);
@@ -275,9 +277,16 @@ static int32_t panel_pack_and_t(dhqr_ctx *c, const double *P, int64_t rows, int6
 // C (rows x ncols) <- (I - V op(T) V') C with op(T) = T' (trans=1) or T (trans=0).
 // phase 0: everything; 1: only Y = V' C and its split-K reduction (needs V, not T: the lane's side stream runs it while the
 // panel is still being verified); 2: the rest (T product + subtraction) on the Y a phase-1 call left in the SAME workspace.
+// The early top of the panel chain splits phase 2 by ROWS (narrow updates only; rsplit a multiple of 128): 3: the T product
+// and the subtraction of rows [0, rsplit) -- final rows of R and the next panel's top block, all k_panel_top needs; 4: the
+// subtraction of rows [rsplit, rows) with the W phase 3 left in the workspace (on the lane's side stream).  The two launches
+// partition the row tiles of the one-launch form and run the same kernel: every row is subtracted exactly once, same bits.
 static int32_t panel_apply(dhqr_ctx *c, const PanelBuf &pb, int64_t rows, double *C, int64_t ncols,
-                           int64_t ldc, int trans, int kw = DHQR_NBV, int phase = 0) {
+                           int64_t ldc, int trans, int kw = DHQR_NBV, int phase = 0, int64_t rsplit = 0) {
   if (ncols <= 0 || rows <= 0) return DHQR_OK;
+  if (phase >= 3 && (kw != DHQR_NBV || ncols > 2 * DHQR_NBV || rsplit % 128 != 0 || rsplit <= 0))
+    return set_err(DHQR_EINVAL, "internal error: row-split narrow update");
+  const int64_t r_lo = phase == 4 ? std::min(rsplit, rows) : 0, r_hi = phase == 3 ? std::min(rsplit, rows) : rows;
   const int64_t ldv = pb.ldv;
   const double *V = pb.V;
   const double *Top = trans ? pb.T : pb.Tt, *TopT = trans ? pb.Tt : pb.T;
@@ -297,7 +306,7 @@ static int32_t panel_apply(dhqr_ctx *c, const PanelBuf &pb, int64_t rows, double
 #define DHQR_APPLY(KW_)                                                                              \
   do {                                                                                               \
     CHECK(prof_begin(c, CAT_VTA));                                                                   \
-    if (phase != 2) {                                                                                \
+    if (phase < 2) {                                                                                 \
     if (vec)                                                                                         \
       hipLaunchKernelGGL((k_gemm_tn<2, 1, KW_>), dim3((unsigned)ntiles, (unsigned)nsplit), dim3(256), 0, \
                          c->stream, V, ldv, (const double *)C, ldc, 1, (int64_t)0, rows, ncols, rps,    \
@@ -311,13 +320,14 @@ static int32_t panel_apply(dhqr_ctx *c, const PanelBuf &pb, int64_t rows, double
     /* (one event ends the previous section and starts this one) */                                                                    \
     const double *w1sum = ws.w1.p;                                                                   \
     if (nsplit > 1) { /* bandwidth-friendly, deterministic split-K reduction */                      \
-      if (phase != 2)                                                                                \
+      if (phase < 2)                                                                                 \
       hipLaunchKernelGGL(k_reduce_splits, dim3((unsigned)((wstride + 63) / 64)), dim3(256), 0,       \
                          c->stream, (const double *)ws.w1.p, (int)nsplit, wstride, wstride, ws.w1r.p); \
       w1sum = ws.w1r.p;                                                                              \
     }                                                                                                \
     if (phase == 1) { CHECK(prof_end(c)); break; }                                                   \
-    if (KW_ == DHQR_NBV && ntiles <= 2) /* the lane's narrow updates: k_tw_fused (dhqr_gemm.h) */    \
+    if (phase == 4) { /* W is in the workspace */ }                                                  \
+    else if (KW_ == DHQR_NBV && ntiles <= 2) /* the lane's narrow updates: k_tw_fused (dhqr_gemm.h) */ \
       hipLaunchKernelGGL((k_tw_fused<false>), dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, c->stream, w1sum, ncols, \
                          TopT, (const double *)nullptr, (const double *)nullptr, ws.w2.p, (int64_t)DHQR_NBV); \
     else                                                                                             \
@@ -326,12 +336,13 @@ static int32_t panel_apply(dhqr_ctx *c, const PanelBuf &pb, int64_t rows, double
                        (int64_t)KW_, ws.w2.p, (int64_t)DHQR_NBV, (int64_t)0);                            \
     CHECK(prof_switch(c, CAT_AVW));                                                                              \
     /* (one event ends the previous section and starts this one) */                                                                   \
-    const int64_t gx_ = (rows + 127) / 128;                                                          \
+    const int64_t gx_ = (r_hi - r_lo + 127) / 128;                                                   \
     const int swz_ = (gx_ >= 16 && ntiles >= 16) ? 1 : 0;                              \
     dim3 grid((unsigned)gx_, (unsigned)ntiles);                                                      \
     if (swz_) grid = dim3((unsigned)((((gx_ + 7) / 8) * ((ntiles + 7) / 8) + 7) / 8 * 512), 1);      \
-    launch_nn_sub<KW_>(c, vec, grid, V, ldv, (const double *)ws.w2.p, (int64_t)DHQR_NBV, C, ldc, rows, ncols, swz_, \
-                       true);                                                                        \
+    if (r_hi > r_lo)                                                                                 \
+    launch_nn_sub<KW_>(c, vec, grid, V + r_lo, ldv, (const double *)ws.w2.p, (int64_t)DHQR_NBV, C + r_lo, ldc, r_hi - r_lo, \
+                       ncols, swz_, true, rows);                                                     \
     CHECK(prof_end(c));                                                                              \
   } while (0)
   if (kw == 32) DHQR_APPLY(32);
@@ -480,6 +491,26 @@ static int32_t gram128(dhqr_ctx *c, const double *X, int64_t ldx, int64_t rows, 
   hipLaunchKernelGGL(k_reduce_splits, dim3(DHQR_NBV * DHQR_NBV / 64), dim3(256), 0, c->stream,
                      (const double *)c->spart.p, (int)nsplit, (int64_t)DHQR_NBV * DHQR_NBV,
                      (int64_t)DHQR_NBV * DHQR_NBV, out);
+  return DHQR_OK;
+}
+// The early Gram of a step's panels: out[j] = X_j' X_j (128 x 128 each, contiguous) for nb ADJACENT 128-column blocks of X over
+// the SAME rows, in one launch plus one reduction -- only the diagonal blocks, not the nb x nb block product.  Slabs and
+// sums per block are those of gram128 on that block alone (the same bits).  part: the split-K partials.
+static int32_t gram128_blocks(dhqr_ctx *c, const double *X, int64_t ldx, int64_t rows, int nb, double *out, Buf &part) {
+  const bool vec = (ldx % 2 == 0) && (rows % 2 == 0) && aligned16(X);
+  const int64_t NN = (int64_t)DHQR_NBV * DHQR_NBV;
+  int64_t nsplit, rps;
+  const bool strips = c->gram_strips && rows >= 1024;
+  if (strips) pick_split(rows, 4, 256, 64, &nsplit, &rps, 256, 64);
+  else pick_split(rows, 1, 512, 256, &nsplit, &rps, 512, 64);
+  CHECK(ensure(c, part, (size_t)nsplit * (size_t)nb * (size_t)NN));
+  const dim3 grid((unsigned)nb, (unsigned)nsplit, strips ? 4 : 1);
+  if (strips && vec) hipLaunchKernelGGL((k_gram_blocks<2, 32>), grid, dim3(256), 0, c->stream, X, ldx, rows, rps, part.p, nb * NN);
+  else if (strips) hipLaunchKernelGGL((k_gram_blocks<1, 32>), grid, dim3(256), 0, c->stream, X, ldx, rows, rps, part.p, nb * NN);
+  else if (vec) hipLaunchKernelGGL((k_gram_blocks<2, 128>), grid, dim3(256), 0, c->stream, X, ldx, rows, rps, part.p, nb * NN);
+  else hipLaunchKernelGGL((k_gram_blocks<1, 128>), grid, dim3(256), 0, c->stream, X, ldx, rows, rps, part.p, nb * NN);
+  hipLaunchKernelGGL(k_reduce_splits, dim3((unsigned)(nb * NN / 64)), dim3(256), 0, c->stream, (const double *)part.p, (int)nsplit,
+                     nb * NN, nb * NN, out);
   return DHQR_OK;
 }
 // out (rows x 128, ld ldo) = X (rows x 128, ld ldx) * Y with negY = -Y given (128 x 128, ld 128)
@@ -684,8 +715,18 @@ static int32_t panel_commit_enqueue(dhqr_ctx *c, hipStream_t stream, double *P, 
 }
 // ev_t != nullptr: the commit is left to the caller (panel_commit_enqueue on a stream that waits for ev_t, recorded here
 // behind k_build_t; the caller records c->ev_commit[panel_idx & 1] behind the commit) -- r6: 12 us less on the lane per panel.
+// Gpre != nullptr (passes == 1 only: the early top of the panel chain, dhqr_dist.h): the panel's Gram matrix, already on the
+// device -- the early Gram of a step's first panel, or k_gram_downdate's for a later one; the first gram128 is skipped.
+// ev_rest != nullptr: the rows of P below its top block are still being brought up to date on another stream, which records
+// ev_rest behind that: with Gpre k_panel_top (which reads G and the top block only) runs first and the wait stands in front
+// of V = P M^{-1}, the first reader of the whole panel; without Gpre it stands in front of the Gram product.
+// ev_g != nullptr: recorded where the panel's Gram matrix is there, in front of k_panel_top (what may run beside the one-workgroup k_panel_top waits for it).
+// A rejected panel climbs the ladder of factor_panel_sync after the run's final synchronisation, i.e. from a true Gram
+// matrix of the fully updated panel.
 static int32_t panel_fast_enqueue(dhqr_ctx *c, double *P, int64_t rows, int64_t ldp, double *alpha, const PanelBuf &pb,
-                                  int passes, int panel_idx, hipEvent_t ev_v = nullptr, hipEvent_t ev_t = nullptr) {
+                                  int passes, int panel_idx, hipEvent_t ev_v = nullptr, hipEvent_t ev_t = nullptr,
+                                  const double *Gpre = nullptr, hipEvent_t ev_rest = nullptr, hipEvent_t ev_g = nullptr) {
+  if (Gpre && passes != 1) return set_err(DHQR_EINVAL, "internal error: a pre-computed Gram matrix needs the one-pass panel");
   const int64_t ldv = pb.ldv;
   const size_t NN = (size_t)DHQR_NBV * DHQR_NBV;
   CHECK(ensure(c, c->rbuf, 2 * panel_rbuf_elems()));
@@ -703,6 +744,7 @@ static int32_t panel_fast_enqueue(dhqr_ctx *c, double *P, int64_t rows, int64_t 
   auto body = [&]() -> int32_t {
     const double *X = P;  // what the reflectors are reconstructed from: the panel, or its explicit Q factor
     int64_t ldx = ldp;
+    if (ev_rest && !Gpre) HIPCHECK(hipStreamWaitEvent(c->stream, ev_rest, 0));
     if (passes == 3) {  // TSQR-HR (dhqr_tsqr.h): R_t and the explicit Q from the tree, replay of Q with R(Q) = I
       TsqrLocal t;
       t.place(c->tsq.p, rows);
@@ -722,8 +764,14 @@ static int32_t panel_fast_enqueue(dhqr_ctx *c, double *P, int64_t rows, int64_t 
       CHECK(gram128(c, Q1, ldq, rows, G));                                         // G2 = Q1'Q1
       launch_chol_inv(c, G, R1, Rf, nullptr, bflag);                                // R  = chol(G2) R1
       launch_recon_top(c, P, ldp, Rf, altmp, Rref, negMinv);                        // alpha, R_ref, -M^{-1}
+    } else if (Gpre) {  // G is there: replay on the top block at once, the rest of the panel may still be on its way
+      if (ev_g) HIPCHECK(hipEventRecord(ev_g, c->stream));
+      hipLaunchKernelGGL((k_panel_top<false>), dim3(1), dim3(1024), 0, c->stream, Gpre, (const double *)P, ldp, altmp, Rref, negMinv,
+                         bflag);
+      if (ev_rest) HIPCHECK(hipStreamWaitEvent(c->stream, ev_rest, 0));
     } else {  // R = chol(P'P), replay, -M^{-1} in one launch
       CHECK(gram128(c, P, ldp, rows, G));
+      if (ev_g) HIPCHECK(hipEventRecord(ev_g, c->stream));
       hipLaunchKernelGGL((k_panel_top<false>), dim3(1), dim3(1024), 0, c->stream, (const double *)G, (const double *)P, ldp, altmp,
                          Rref, negMinv, bflag);
     }
@@ -1379,6 +1427,7 @@ int32_t dhqr_create(dhqr_ctx **out, int32_t device) {
     { long long v; if (tune_get("qtb_vec", &v)) c->qtb_vec = (int)v; }
     { long long v; if (tune_get("gram_strips", &v)) c->gram_strips = v != 0; }
     { long long v; if (tune_get("fuse_fix", &v)) c->fuse_fix = v != 0; }
+    { long long v; if (tune_get("early_top", &v)) c->early_top = std::max(0, std::min(2, (int)v)); }
     { long long v; if (tune_get("commit_off", &v)) c->commit_off = (int)v; }
     hipLaunchKernelGGL(k_set_status, dim3(1), dim3(64), 0, c->stream, c->dstat, INT_MAX);
     LAUNCHCHECK();
@@ -1417,7 +1466,7 @@ int32_t dhqr_destroy(dhqr_ctx *c) {
     c->hio = nullptr;
   }
   Buf *bufs[] = {&c->vbuf, &c->vt, &c->vts, &c->ws[0].w1, &c->ws[0].w1r, &c->ws[0].w2, &c->ws[1].w1,
-                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp, &c->batch_dev, &c->f32_ws, &c->f32_dev};
+                 &c->ws[1].w1r, &c->ws[1].w2, &c->ws[2].w1, &c->ws[2].w1r, &c->ws[2].w2, &c->spart, &c->spart2, &c->sfull, &c->scratch, &c->pbuf, &c->rbuf, &c->tsq, &c->zsolve_lo, &c->host_mat, &c->sv_T, &c->sv_S, &c->sv_part, &c->sv_small, &c->tc_T, &c->tc_alpha, &c->small_dev, &c->sv_bkp, &c->batch_dev, &c->f32_ws, &c->f32_dev, &c->gold, &c->gpart};
   for (Buf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (auto &e : c->evs) {

@@ -37,6 +37,10 @@ struct CsState {
   hipEvent_t ev_ready[2 * CS_EVR], ev_recv[2 * CS_EVR];
   hipEvent_t ev_v[2 * CS_EVR], ev_y[2 * CS_EVR], ev_x[CS_EVR];  // lane side stream: V of a panel final / Y = V_a' C_b done / a group's cross terms done
   hipEvent_t ev_t[2 * CS_EVR];  // a panel's T and verdict are final (k_build_t done): what its off-lane commit waits for
+  // early top, second panel b of a pair (a, b): ev_w[b] the lane has W and the top rows of the narrow update onto block b,
+  // ev_r[b] the side stream has the rest of the rows (the same for panel c of a quad (a, b)(c, d) and the first pair's update);
+  // ev_g[a] panel a's Gram matrix is there (k_panel_top is next), ev_gb[a] the side stream has Gold_b
+  hipEvent_t ev_w[2 * CS_EVR], ev_r[2 * CS_EVR], ev_g[2 * CS_EVR], ev_gb[2 * CS_EVR];
   hipEvent_t ev_start = nullptr, ev_end = nullptr;
   int64_t ticket[2 * CS_EVR];
   Buf gbuf[CS_NGB];
@@ -63,6 +67,10 @@ static int32_t cs_state_init(dhqr_ctx *c) {
     HIPCHECK(hipEventCreateWithFlags(&s.ev_v[i], hipEventDisableTiming));
     HIPCHECK(hipEventCreateWithFlags(&s.ev_y[i], hipEventDisableTiming));
     HIPCHECK(hipEventCreateWithFlags(&s.ev_t[i], hipEventDisableTiming));
+    HIPCHECK(hipEventCreateWithFlags(&s.ev_w[i], hipEventDisableTiming));
+    HIPCHECK(hipEventCreateWithFlags(&s.ev_r[i], hipEventDisableTiming));
+    HIPCHECK(hipEventCreateWithFlags(&s.ev_g[i], hipEventDisableTiming));
+    HIPCHECK(hipEventCreateWithFlags(&s.ev_gb[i], hipEventDisableTiming));
     s.ticket[i] = -1;
   }
   HIPCHECK(hipEventCreateWithFlags(&s.ev_start, hipEventDisableTiming));
@@ -87,6 +95,10 @@ static void cs_state_free(dhqr_ctx *c) {
       (void)hipEventDestroy(s.ev_v[i]);
       (void)hipEventDestroy(s.ev_y[i]);
       (void)hipEventDestroy(s.ev_t[i]);
+      (void)hipEventDestroy(s.ev_w[i]);
+      (void)hipEventDestroy(s.ev_r[i]);
+      (void)hipEventDestroy(s.ev_g[i]);
+      (void)hipEventDestroy(s.ev_gb[i]);
     }
     (void)hipEventDestroy(s.ev_start);
     (void)hipEventDestroy(s.ev_end);
@@ -327,6 +339,23 @@ static int32_t cs_run(const CsProblem &pr, int64_t kstart, bool robust_first, in
     };
     bool merged_update = false;
     bool v_event[2] = {false, false};  // ev_v recorded for panel idx of this group (this rank, fast path)
+    // The early top of the panel chain (DHQR_TUNE early_top), in-pair form: both panels of the pair are local, adjacent and
+    // on the one-pass fast path.  Block b is brought up to date together with block a (merged_update), so its Gram matrix
+    // over the rows of panel a, Gold_b, can be taken before panel a is factored: on the side stream, beside k_panel_top of
+    // panel a (one workgroup; the chip is idle otherwise).  Panel b's own Gram matrix follows by downdate with the 128 rows
+    // of R that panel a leaves in block b (k_gram_downdate).  Those rows and panel b's top block are the first 256 rows
+    // of the narrow update C_b -= V_a W: k_panel_top of panel b starts behind them, the rest of the rows follows on the
+    // side stream and is waited for in front of V_b = P_b M^{-1}.  Without a side stream (P > 1) the same arithmetic
+    // runs on the lane.
+    const size_t NN_ = (size_t)NB * NB;
+    const bool early_pair = c->early_top != 0 && gr.np == 2 && c->cholqr_passes == 1 && pr.mine(gr.a) && pr.mine(gr.a + 1) &&
+                            pr.lcol(gr.a + 1) == pr.lcol(gr.a) + NB && pr.width(gr.a) == NB &&
+                            panel_fast_eligible(c, m - (gr.a + 1) * NB, pr.width(gr.a + 1)) && !(robust_first && gr.a == kstart);
+    const bool early_gram = early_pair && c->early_top == 1;  // (early_top = 2: the split update with the true Gram matrices)
+    double *gold = c->gold.p ? c->gold.p + (size_t)(h & 1) * 2 * NN_ : nullptr;
+    hipEvent_t ev_rest = nullptr;  // panel b: the rest of its rows is on its way on the side stream
+    hipEvent_t ev_rest_a = nullptr;  // panel a = c of a quad (a, b)(c, d): the same for the first pair's update of [c d]
+    bool commit_a_side = false;    // panel a's commit runs on the side stream behind those rows, not in front of W on the lane
     for (int idx = 0; idx < gr.np; ++idx) {
       const int64_t x = gr.a + idx, w = pr.width(x), rows = m - x * NB;
       const PanelBuf pbx = idx == 0 ? gb.pa() : gb.pb();
@@ -354,7 +383,50 @@ static int32_t cs_run(const CsProblem &pr, int64_t kstart, bool robust_first, in
             merged_update = true;
           }
           CHECK(lane_begin(was));
-          const int32_t rc = second_of_quad ? apply_group(prev, lc, ncols) : apply_step(sh - 1, lc, ncols);
+          int32_t rc = DHQR_OK;
+          if (early_pair && second_of_quad && merged_update && side && v_final[(size_t)prev] && groups[prev].np == 2) {
+            // Early top at the pair boundary inside a quad: the first pair (a, b) reaches the block [c d] in three parts.
+            // Side stream: Gold_c = C_c'C_c over the rows of panel a as soon as the block carries everything before the
+            // step, then Y = [V_a V_b]' C behind "V_b final" -- beside panel b's second Gram product, k_build_t and commit.
+            // Lane: W (needs T_b and V_b'V_a: the lane is behind both), the first 512 rows of C -= [V_a V_b] W -- the 256
+            // final rows of R above panel c (and above panel d, as far as this pair goes) and the two top blocks --, the
+            // downdate G_c = Gold_c - R'R, and k_panel_top of panel c.  Side stream: the rest of the rows, waited for in
+            // front of V_c = P_c M^{-1}.  The launches partition the row tiles of pair_apply's one subtraction.
+            const CsGroup &g1r = groups[prev];
+            const CsGroupBuf g1 = gview(prev);
+            double *C = pr.A + g1r.a * NB + lc * lda;
+            const int64_t ld2 = 2 * NB, rows1 = g1.rows_a, rtop = std::min<int64_t>(4 * NB, rows1);
+            const bool vec = (lda % 2 == 0) && (g1.ldv % 2 == 0) && (rows1 % 2 == 0) && aligned16(C) && aligned16(g1.VA);
+            const int pl_ = (int)(g1r.last() % (2 * CS_EVR));
+            c->epoch = (int)g1r.last();
+            on(sX, 2);
+            if (sh >= 1) HIPCHECK(hipStreamWaitEvent(sX, (has_head(sh - 1) ? S.ev_head : S.ev_wide)[(sh - 1) % CS_EVR], 0));
+            if (early_gram) rc = gram128_blocks(c, C, lda, rows1, 1, gold, c->gpart);
+            HIPCHECK(hipStreamWaitEvent(sX, S.ev_v[pl_], 0));
+            dhqr_ctx::WS &ws2 = c->ws[2];
+            if (rc == DHQR_OK) rc = narrow_vtc(c, g1.VA, g1.ldv, rows1, C, lda, ncols, vec, ws2.w1, ws2.w1r.p);
+            HIPCHECK(hipEventRecord(S.ev_y[pe], sX));
+            on(sL, 2);
+            HIPCHECK(hipStreamWaitEvent(sL, S.ev_y[pe], 0));
+            if (rc == DHQR_OK) rc = pair_tw(c, ws2.w1r.p, g1.pa().T, g1.pb().T, g1.Sba, ws2.w2.p, ld2, ncols);
+            launch_nn_sub<256>(c, vec, dim3((unsigned)((rtop + 127) / 128), 2), g1.VA, g1.ldv, (const double *)ws2.w2.p, ld2, C, lda, rtop,
+                               ncols, 0, true, rows1);
+            if (early_gram)
+              hipLaunchKernelGGL(k_gram_downdate, dim3(64), dim3(256), 0, sL, (const double *)gold, (const double *)C, lda, (int)(2 * NB),
+                                 gold, (const int *)c->dstat, c->epoch);
+            HIPCHECK(hipEventRecord(S.ev_w[pe], sL));
+            on(sX, 2);
+            HIPCHECK(hipStreamWaitEvent(sX, S.ev_w[pe], 0));
+            if (rows1 > rtop)
+              launch_nn_sub<256>(c, vec, dim3((unsigned)((rows1 - rtop + 127) / 128), 2), g1.VA + rtop, g1.ldv, (const double *)ws2.w2.p,
+                                 ld2, C + rtop, lda, rows1 - rtop, ncols, 0, true, rows1);
+            HIPCHECK(hipEventRecord(S.ev_r[pe], sX));
+            ev_rest_a = S.ev_r[pe];
+            on(sL, 1);
+            LAUNCHCHECK();
+          } else {
+            rc = second_of_quad ? apply_group(prev, lc, ncols) : apply_step(sh - 1, lc, ncols);
+          }
           CHECK(lane_end(was));
           CHECK(rc);
         }
@@ -365,7 +437,37 @@ static int32_t cs_run(const CsProblem &pr, int64_t kstart, bool robust_first, in
           CHECK(lane_begin(was));
           c->epoch = (int)gr.a;
           int32_t rc = DHQR_OK;
-          if (side && v_event[0] && (merged_update || prev < 0)) {
+          if (early_pair && side && v_event[0]) {
+            const int pb_ = (int)(x % (2 * CS_EVR));
+            on(sX, 2);
+            HIPCHECK(hipStreamWaitEvent(sX, S.ev_v[pa_], 0));
+            rc = panel_apply(c, gb.pa(), gb.rows_a, Cb, w, lda, 1, DHQR_NBV, 1);  // Y = V_a' C_b
+            HIPCHECK(hipEventRecord(S.ev_y[pa_], sX));
+            on(sL, 2);
+            HIPCHECK(hipStreamWaitEvent(sL, S.ev_y[pa_], 0));
+            if (rc == DHQR_OK) rc = panel_apply(c, gb.pa(), gb.rows_a, Cb, w, lda, 1, DHQR_NBV, 3, 2 * NB);  // W, rows [0, 256)
+            if (early_gram) {
+              HIPCHECK(hipStreamWaitEvent(sL, S.ev_gb[pa_], 0));  // Gold_b (long done)
+              hipLaunchKernelGGL(k_gram_downdate, dim3(64), dim3(256), 0, sL, (const double *)(gold + NN_), (const double *)Cb, lda,
+                                 (int)NB, gold + NN_, (const int *)c->dstat, (int)gr.a);
+            }
+            HIPCHECK(hipEventRecord(S.ev_w[pb_], sL));
+            on(sX, 2);
+            HIPCHECK(hipStreamWaitEvent(sX, S.ev_w[pb_], 0));
+            hipLaunchKernelGGL(k_zero_rows, dim3(DHQR_NBV), dim3(128), 0, sX, gb.VB, gb.ldv, (int)NB);
+            if (rc == DHQR_OK) rc = panel_apply(c, gb.pa(), gb.rows_a, Cb, w, lda, 1, DHQR_NBV, 4, 2 * NB);  // rows [256, rows)
+            if (commit_a_side) {
+              // panel a's commit (its T and verdict are final: the lane has passed k_build_t): the lane's wait for ev_r also
+              // orders it in front of panel a + 2, the next user of this parity's scratch set
+              if (rc == DHQR_OK)
+                rc = panel_commit_enqueue(c, sX, pr.A + gr.a * NB + pr.lcol(gr.a) * lda, gb.rows_a, lda, pr.alpha + gr.a * NB, gb.pa(),
+                                          (int)gr.a);
+              HIPCHECK(hipEventRecord(S.ev_ready[pa_], sX));
+            }
+            HIPCHECK(hipEventRecord(S.ev_r[pb_], sX));
+            ev_rest = S.ev_r[pb_];
+            on(sL, 1);
+          } else if (side && v_event[0] && (merged_update || prev < 0)) {
             // Y = V_a' C_b on the side stream as soon as V_a is final (block b was brought up to date together with block a,
             // before panel a was factored -- merged_update -- so ev_v is recorded behind that on the lane); T_a' Y and the
             // subtraction follow on the lane once panel a is verified and committed.  Both calls see workspace 2.
@@ -382,16 +484,33 @@ static int32_t cs_run(const CsProblem &pr, int64_t kstart, bool robust_first, in
           }
           CHECK(lane_end(was));
           CHECK(rc);
-          hipLaunchKernelGGL(k_zero_rows, dim3(DHQR_NBV), dim3(128), 0, sL, gb.VB, gb.ldv, (int)NB);
+          if (!ev_rest) {
+            hipLaunchKernelGGL(k_zero_rows, dim3(DHQR_NBV), dim3(128), 0, sL, gb.VB, gb.ldv, (int)NB);
+            if (early_gram)  // no side stream: the whole update has run on the lane, the same downdate follows
+              hipLaunchKernelGGL(k_gram_downdate, dim3(64), dim3(256), 0, sL, (const double *)(gold + NN_), (const double *)Cb, lda,
+                                 (int)NB, gold + NN_, (const int *)c->dstat, (int)gr.a);
+          }
         }
+        if (idx == 0 && early_gram && !side)  // Gold_b over the rows of panel a: block b carries everything before the pair
+          CHECK(gram128_blocks(c, pr.A + x * NB + (lc + NB) * lda, lda, rows, 1, gold + NN_, c->gpart));
         double *Pp = pr.A + x * NB + lc * lda;
         c->epoch = saved_epoch;
         c->tt_keep = (c->tc_base && P == 1) ? c->tc_base + x * (NB * NB) : nullptr;  // kept T factors (dhqr_api.hip)
         bool deferred = false;
         if (panel_fast_eligible(c, rows, w) && !(robust_first && x == kstart)) {
           deferred = sK != nullptr;
+          if (idx == 0) commit_a_side = early_pair && side && !deferred && !c->panel_hook;
           CHECK(panel_fast_enqueue(c, Pp, rows, lda, pr.alpha + x * NB, pbx, c->cholqr_passes, (int)x, side ? S.ev_v[pe] : nullptr,
-                                   deferred ? S.ev_t[pe] : nullptr));
+                                   deferred || (commit_a_side && idx == 0) ? S.ev_t[pe] : nullptr,
+                                   early_gram && idx == 1 ? gold + NN_ : (early_gram && ev_rest_a ? gold : nullptr),
+                                   idx == 1 ? ev_rest : ev_rest_a, early_gram && idx == 0 && side ? S.ev_g[pe] : nullptr));
+          if (early_gram && idx == 0 && side) {  // Gold_b on the side stream behind panel a's Gram product: beside k_panel_top
+            on(sX, 2);
+            HIPCHECK(hipStreamWaitEvent(sX, S.ev_g[pe], 0));
+            CHECK(gram128_blocks(c, pr.A + x * NB + (lc + NB) * lda, lda, rows, 1, gold + NN_, c->gpart));
+            HIPCHECK(hipEventRecord(S.ev_gb[pe], sX));
+            on(sL, 1);
+          }
           v_event[idx] = side;
           fast_idx.push_back(x);
         } else {
@@ -417,7 +536,7 @@ static int32_t cs_run(const CsProblem &pr, int64_t kstart, bool robust_first, in
           HIPCHECK(hipStreamWaitEvent(sK, S.ev_t[pe], 0));
           CHECK(commit_on(sK, 0));
           HIPCHECK(hipEventRecord(S.ev_ready[pe], sK));
-        } else if (!deferred) {
+        } else if (!deferred && !(commit_a_side && idx == 0)) {
           HIPCHECK(hipEventRecord(S.ev_ready[pe], sL));
         }
         // host-in / host-out drop-in: the column block of a committed panel is final and may leave for the host
@@ -557,6 +676,9 @@ static int32_t cs_prepare(const CsProblem &pr) {
   CHECK(ensure(c, c->spart2, (size_t)512 * NN));  // the same for the cross terms built on the lane's side stream
   CHECK(ensure(c, c->sfull, NN));
   CHECK(ensure(c, c->rbuf, 2 * panel_rbuf_elems()));
+  // early top: the early Gram matrix of a pair's second block (two sets of two, by group parity) and its split-K partials
+  CHECK(ensure(c, c->gold, 4 * NN));
+  CHECK(ensure(c, c->gpart, (size_t)256 * NN));
   if (c->cholqr_passes == 3) CHECK(ensure(c, c->tsq, TsqrLocal::elems(m)));  // TSQR-HR for every panel
   CHECK(ensure(c, c->scratch, 4096));
   return DHQR_OK;

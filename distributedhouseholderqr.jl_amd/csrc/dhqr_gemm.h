@@ -254,6 +254,18 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn(const double *__restrict__ V
                                      blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
+// The DIAGONAL Gram blocks of several adjacent 128-column blocks of X in one launch (gram128_blocks in dhqr_api.hip: the
+// early Gram of a step's panels): blockIdx.x = block j, G_j = X_j' X_j over the same rows, not the (j, k) products.  The
+// partial of row slab s lands at out + s * osplit_stride + j * 128 * 128; blockIdx.z = strip of NBV rows of G_j as in the
+// strip form of gram128 -- per block the launch is that of k_gemm_tn on X_j alone (same slabs, same sums, same bits).
+template <int VEC, int NBV>
+__global__ __launch_bounds__(256, 2) void k_gram_blocks(const double *__restrict__ X, int64_t ldx, int64_t rows, int64_t rps,
+                                                        double *__restrict__ out, int64_t osplit_stride) {
+  const double *Xj = X + (int64_t)blockIdx.x * 128 * ldx;
+  gemm_tn_body<VEC, 1, NBV, 0>(Xj, ldx, Xj, ldx, 1, 0, rows, 128, rps, out + (int64_t)blockIdx.x * 128 * 128, 128, osplit_stride,
+                               0u, blockIdx.y, blockIdx.z);
+}
+
 // Batched Gram products of the solve (dhqr_qtb.h): S_k = V_k' V_k for EVERY 128-column panel of a factored matrix in one
 // launch, V_k read in place (MASK).  unit_first[k] = index of panel k's first (panel, rps-row slab) unit, unit_first[np] =
 // number of units = gridDim.x; unit u of panel k writes its 128 x 128 partial sum to out + u * 128 * 128 (summed in slab

@@ -126,6 +126,13 @@ struct dhqr_ctx {
   int tn2_rgroups = 1;   // row groups of a stream-K k_gemm_tn2 launch (dhqr_gemm.h: tn2_sk_group_of): 1 / 2 / 4 / 8, 0 = by height
   int64_t tn2_rg8_rows = 20480, tn2_rg4_rows = 10240, tn2_rg2_rows = 5120;
   int fuse_fix = 1;      // k_recon_fix in the epilogue of V = P M^{-1} (mul128; DHQR_TUNE fuse_fix=0: its own launch)
+  int early_top = 1;     // the early top of the panel chain (dhqr_dist.h): a pair's second panel, and the third panel of a
+                         // quad step, get their Gram matrix by downdate (k_gram_downdate) and start k_panel_top once the
+                         // top rows of the narrow update are done, the rest of the rows follow on the side stream.
+                         // DHQR_TUNE early_top=0: the chain as it was; 2: the split update with the true Gram matrices
+                         // (bit-identical to 0: test / A-B aid)
+  Buf gold;              // ... early Gram matrices, two sets by group parity of [first block (a quad's second pair) | second block]
+  Buf gpart;             // ... their split-K partials (one product in flight at a time: lane or side stream, in order)
   int commit_off = -1;   // an accepted panel's commit (12 us of copies into the matrix) leaves the lane: -1 (default) with more
                          // than one rank, where it runs on the communication stream BEHIND the panel's broadcast; 0 never;
                          // 1 also at one rank, on a stream of its own -- measured there (profiles/r06_ab_chain.txt): a

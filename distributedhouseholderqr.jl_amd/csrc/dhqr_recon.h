@@ -612,6 +612,38 @@ __global__ __launch_bounds__(1024) void k_panel_top(const double *__restrict__ G
   rc_chol_replay_invert<TIME>(g, a, rbuf, wrow, vcol, L, alpha, Rref, negMinv, flag);
 }
 
+// Gram matrix of a panel by DOWNDATE (the early top of the panel chain, dhqr_dist.h): Gold = C'C of a 128-column block
+// over the rows from the first panel of its step on, taken before the step's reflectors reached the block.  Those
+// reflectors are orthogonal and act on exactly these rows, so once they are applied the Gram matrix of the panel proper
+// is Gold - R'R with R = the rows above the panel's diagonal block inside the step (nrows = 128, 256 or 384 final rows
+// of the factor R; R points at the first of them, leading dimension ldr).  k_panel_top then starts before the rest of
+// the block's rows has been updated.  64 workgroups, one 16 x 16 tile each; plain FMA in row order: G(i,j) and G(j,i)
+// are the same sum of the same commuting products, so G is symmetric to the bit, and nothing depends on timing.
+// G may alias Gold.  The relative accuracy of G_jj is that of Gold_jj times Gold_jj / G_jj; a panel that lies almost in
+// the span of the step's earlier panels ends in the device-side rejection like any other bad Gram matrix.
+__global__ __launch_bounds__(256) void k_gram_downdate(const double *Gold, const double *__restrict__ R, int64_t ldr,
+                                                       int nrows, double *G, const int *__restrict__ stat, int epoch) {
+  __shared__ double Ri[128][17], Rj[128][17];
+  if (stat != nullptr && stat[0] <= epoch) return;  // uniform
+  const int t = threadIdx.x, ti = t & 15, tj = t >> 4;
+  const int i0 = (blockIdx.x & 7) * 16, j0 = (blockIdx.x >> 3) * 16;
+  double s = 0.0;
+  for (int r0 = 0; r0 < nrows; r0 += 128) {
+    if (r0) __syncthreads();  // the previous chunk has been read
+    for (int e = t; e < 128 * 16; e += 256) {
+      const int r = e & 127, cc = e >> 7;
+      const bool ok = r0 + r < nrows;
+      Ri[r][cc] = ok ? R[r0 + r + (int64_t)(i0 + cc) * ldr] : 0.0;
+      Rj[r][cc] = ok ? R[r0 + r + (int64_t)(j0 + cc) * ldr] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int r = 0; r < 128; ++r) s = fma(Ri[r][ti], Rj[r][tj], s);
+  }
+  const int idx = (i0 + ti) + (j0 + tj) * RC_N;
+  G[idx] = Gold[idx] - s;
+}
+
 // Vw currently holds P * M^{-1}; finish V = tril((P - alpha E) M^{-1}) on the top 128 rows:
 // Vw[i][j] -= alpha_i * Minv[i][j] (i <= j ... only i == row index < 128), and zero above the diagonal.
 __global__ __launch_bounds__(256) void k_recon_fix(double *__restrict__ Vw, int64_t ldv,
