@@ -266,10 +266,12 @@ def rand_colmajor_c(m: int, n: int, seed: int, device="cuda"):
 # ------------------------------------------------------------------------------- API mirror
 class DistributedHouseholderQRStruct:
     """src:296-309: the factored matrix `A` (V on/below the diagonal, R strictly above) and
-    `α` = diag(R).  `alpha` is an ASCII alias of `α`."""
+    `α` = diag(R).  `alpha` is an ASCII alias of `α`.  `jpvt`: None, or the (batch, n) int32 column permutation of a
+    pivoted factorisation (qr_pivoted_batched_): A[k][:, jpvt[k]] = Q[k] R[k]."""
 
-    def __init__(self, A, α=None):
+    def __init__(self, A, α=None, jpvt=None):
         self.A = A
+        self.jpvt = jpvt
         if α is None:  # src:306-309  α = zeros(eltype(A), size(A, 2)); a batch (batch, m, n) has one α per matrix: (batch, n)
             shape = tuple(A.shape[:-2]) + (A.shape[-1],)
             α = torch.zeros(shape, dtype=A.dtype, device=A.device) if _is_tensor(A) else np.zeros(shape, dtype=A.dtype)
@@ -711,6 +713,172 @@ def ldiv_batched(H: DistributedHouseholderQRStruct, b):
                                   al.ctypes.data_as(ctypes.c_void_p), sal, bb.ctypes.data_as(ctypes.c_void_p), sb,
                                   x.ctypes.data_as(ctypes.c_void_p), max(n, 1), batch))
     return x
+
+
+# ------------------------------------------------------------------------------- column pivoting, rank, truncated solve
+def _is_f64(x) -> bool:
+    return x.dtype == (torch.float64 if _is_tensor(x) else np.float64)
+
+
+def _vp(x):
+    return ctypes.c_void_p(x.data_ptr()) if _is_tensor(x) else x.ctypes.data_as(ctypes.c_void_p)
+
+
+def _pivoted_input(A, what):
+    """the (batch, m, n) float64 view of the argument of the pivoted functions (a 2-D A is a batch of one) and whether it
+    lives on the device; float32 and complex input is a TypeError (dhqr.h: Float64 only)"""
+    if not (_is_tensor(A) or isinstance(A, np.ndarray)):
+        raise TypeError(f"{what}: float64 numpy array or CUDA tensor expected")
+    if not _is_f64(A):
+        raise TypeError(f"{what}: the pivoted routes are float64 only, got {A.dtype}")
+    if A.ndim == 2:
+        A = A[None]
+    if A.ndim != 3:
+        raise ValueError(f"{what}: (batch, m, n) or (m, n) array expected")
+    if _is_tensor(A) and not A.is_cuda:
+        raise TypeError(f"{what}: device path needs a float64 CUDA tensor")
+    return A, _is_tensor(A)
+
+
+def _rcond(rcond) -> float:
+    return -1.0 if rcond is None else float(rcond)
+
+
+def qr_pivoted_batched_(A) -> DistributedHouseholderQRStruct:
+    """qr!(A[k]) with COLUMN PIVOTING for every matrix of a (batch, m, n) float64 batch (a 2-D A is a batch of one) in one
+    call (dhqr_factor_batched_pivoted_f64 on a CUDA tensor with column-major matrices, dhqr_qr_batched_pivoted_f64 on a
+    numpy array): A[k][:, jpvt[k]] = Q[k] R[k].  Mutates A; returns the struct with α (batch, n) and jpvt (batch, n) int32.
+    get_q, get_r and apply_q_ take the struct unchanged."""
+    L = _lib.lib()
+    A, dev = _pivoted_input(A, "A")
+    batch, m, n = A.shape
+    if dev:
+        lay = _batch_layout(A.shape, A.stride())
+        if lay is None:
+            raise ValueError("matrices of the batch must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
+        H = DistributedHouseholderQRStruct(A, jpvt=torch.zeros((batch, n), dtype=torch.int32, device=A.device))
+        ctx = get_context(A.device.index)
+        ctx.use_torch_stream()
+        check(L.dhqr_factor_batched_pivoted_f64(ctx.handle, _vp(A), m, n, lay[0], lay[1], _vp(H.α), max(n, 1), _vp(H.jpvt), max(n, 1),
+                                                batch))
+        ctx.synchronize()
+        return H
+    F, lda, strideA = _host_batch(A)
+    H = DistributedHouseholderQRStruct(A, jpvt=np.zeros((batch, n), dtype=np.int32))
+    check(L.dhqr_qr_batched_pivoted_f64(get_context().handle, _vp(F), m, n, lda, strideA, _vp(H.α), max(n, 1), _vp(H.jpvt), max(n, 1),
+                                        batch))
+    if F is not A:
+        A[...] = F
+    return H
+
+
+def _pivoted_struct(H):
+    """(A (batch, m, n), α, jpvt, on the device?) of a struct qr_pivoted_batched_ returned"""
+    if getattr(H, "jpvt", None) is None:
+        raise TypeError("a pivoted factorisation (qr_pivoted_batched_) expected: the struct has no jpvt")
+    A, dev = _pivoted_input(H.A, "H.A")
+    batch, m, n = A.shape
+    _same_dtype(A, H.α, "α")
+    xp = torch if dev else np
+    for v, dt, name in ((H.α, xp.float64, "α"), (H.jpvt, xp.int32, "jpvt")):
+        if _is_tensor(v) != dev or v.dtype != dt or tuple(v.shape) != (batch, n) or (dev and not (v.is_cuda and v.is_contiguous())):
+            raise TypeError(f"{name} must be a contiguous {dt} {'CUDA tensor' if dev else 'numpy array'} of shape ({batch}, {n})")
+    if dev:
+        return A, H.α, H.jpvt, True
+    return A, np.ascontiguousarray(H.α), np.ascontiguousarray(H.jpvt), False
+
+
+def rank_batched(H: DistributedHouseholderQRStruct, rcond=None):
+    """the numerical rank of every matrix of a pivoted factorisation (dhqr_rank_batched_f64): the number of leading j with
+    |α_j| > rc |α_0|, rc = rcond, or max(m, n) eps when rcond is None or negative; (batch,) int32, where the factor is."""
+    L = _lib.lib()
+    A, α, _, dev = _pivoted_struct(H)
+    batch, m, n = A.shape
+    if dev:
+        rank = torch.zeros((batch,), dtype=torch.int32, device=A.device)
+        _call_small_family(A, L.dhqr_rank_batched_f64, _vp(α), m, n, max(n, 1), _rcond(rcond), _vp(rank), batch)
+        return rank
+    if batch == 0 or n == 0:
+        return np.zeros((batch,), dtype=np.int32)
+    ctx = get_context()
+    ctx.use_torch_stream()
+    d = torch.from_numpy(α).to(f"cuda:{ctx.device}")
+    rank = torch.zeros((batch,), dtype=torch.int32, device=d.device)
+    check(L.dhqr_rank_batched_f64(ctx.handle, _vp(d), m, n, n, _rcond(rcond), _vp(rank), batch))
+    ctx.synchronize()
+    return rank.cpu().numpy()
+
+
+def _rhs_block(b, batch, m, dev, what="b"):
+    """(B (batch, m, nrhs), was it (batch, m)?) of the right-hand sides of the pivoted solves"""
+    if _is_tensor(b) != dev or (dev and not b.is_cuda):
+        raise TypeError(f"{what}: a {'float64 CUDA tensor' if dev else 'float64 numpy array'} like the matrices expected")
+    if not _is_f64(b):
+        raise TypeError(f"{what} is {b.dtype} but the pivoted routes are float64 only: convert it explicitly")
+    vec = b.ndim == 2
+    if vec:
+        b = b[:, :, None]
+    if b.ndim != 3 or tuple(b.shape[:2]) != (batch, m):
+        raise ValueError(f"{what} must have shape ({batch}, {m}) or ({batch}, {m}, nrhs)")
+    return b, vec
+
+
+def ldiv_pivoted_batched(H: DistributedHouseholderQRStruct, B, rcond=None):
+    """the rank-truncated least-squares solution of every matrix of a pivoted factorisation: rank_batched(H, rcond), then
+    dhqr_solve_batched_pivoted_f64 on a copy of B.  B (batch, m) -> X (batch, n); B (batch, m, nrhs) -> X (batch, n, nrhs),
+    column-major matrices.  X[k][jpvt[k][i]] = z_i for i < rank, exact zeros elsewhere; B is not modified."""
+    L = _lib.lib()
+    A, α, jpvt, dev = _pivoted_struct(H)
+    batch, m, n = A.shape
+    B, vec = _rhs_block(B, batch, m, dev, "B")
+    nrhs = B.shape[2]
+    ctx = get_context(A.device.index if dev else None)
+    ctx.use_torch_stream()
+    device = A.device if dev else f"cuda:{ctx.device}"
+    if dev:
+        dA, dal, djp = A, α, jpvt
+    else:  # (the C ABI has no host form of the solve alone: stage with torch)
+        dA = empty_colmajor_batched(batch, m, n, device)
+        dA.copy_(torch.from_numpy(np.ascontiguousarray(A)))
+        dal, djp = torch.from_numpy(α).to(device), torch.from_numpy(jpvt).to(device)
+    lay = _batch_layout(dA.shape, dA.stride())
+    if lay is None:
+        raise ValueError("matrices of the batch must be column-major (stride(1) == 1)")
+    rank = torch.zeros((batch,), dtype=torch.int32, device=device)
+    W = empty_colmajor_batched(batch, m, nrhs, device)
+    W.copy_(B if dev else torch.from_numpy(np.ascontiguousarray(B)))
+    X = empty_colmajor_batched(batch, n, nrhs, device)
+    check(L.dhqr_rank_batched_f64(ctx.handle, _vp(dal), m, n, max(n, 1), _rcond(rcond), _vp(rank), batch))
+    check(L.dhqr_solve_batched_pivoted_f64(ctx.handle, _vp(dA), m, n, lay[0], lay[1], _vp(dal), max(n, 1), _vp(djp), max(n, 1), _vp(rank),
+                                           _vp(W), nrhs, max(m, 1), max(m * nrhs, 1), _vp(X), max(n, 1), max(n * nrhs, 1), batch))
+    ctx.synchronize()
+    if not dev:
+        X = X.cpu().numpy()
+    return X[:, :, 0] if vec else X
+
+
+def lstsq_batched(A, B, rcond=None):
+    """min ||A[k] x - B[k]|| for every matrix of a (batch, m, n) float64 batch, rank-deficient matrices included: column-pivoted
+    QR of a copy, the rank at rcond (rank_batched), the truncated solve.  Returns (X, rank); A and B are not modified.  numpy
+    arrays: dhqr_lstsq_batched_f64; CUDA tensors: the three device entry points on copies."""
+    L = _lib.lib()
+    A, dev = _pivoted_input(A, "A")
+    batch, m, n = A.shape
+    B, vec = _rhs_block(B, batch, m, dev, "B")
+    nrhs = B.shape[2]
+    if dev:
+        W = empty_colmajor_batched(batch, m, n, A.device)
+        W.copy_(A)
+        H = qr_pivoted_batched_(W)
+        X = ldiv_pivoted_batched(H, B, rcond)
+        return (X[:, :, 0] if vec else X), rank_batched(H, rcond)
+    F, lda, strideA = _host_batch(A)
+    Bf, ldb, strideB = _host_batch(B)
+    X = np.zeros((batch, nrhs, n), dtype=np.float64).transpose(0, 2, 1)
+    rank = np.zeros((batch,), dtype=np.int32)
+    check(L.dhqr_lstsq_batched_f64(get_context().handle, _vp(F), m, n, lda, strideA, _vp(Bf), nrhs, ldb, strideB, _rcond(rcond), _vp(X),
+                                   max(n, 1), max(n * nrhs, 1), _vp(rank), batch))
+    return (X[:, :, 0] if vec else X), rank
 
 
 def _partialdot_c64(a, b, lo: int, hi: int) -> complex:

@@ -40,7 +40,9 @@ extern "C" {
                           * dhqr_solve_batched_nrhs_f64, dhqr_ldiv_batched_nrhs_f64, dhqr_solve_batched_nrhs_f32,
                           * dhqr_ldiv_batched_nrhs_f32;
                           * dhqr_factor_batched_c64, dhqr_solve_batched_c64, dhqr_qr_batched_c64, dhqr_ldiv_batched_c64;
-                          * the one-workgroup ComplexF64 route up to 128 rows behind the existing dhqr_*_c64 names (no new symbol) */
+                          * the one-workgroup ComplexF64 route up to 128 rows behind the existing dhqr_*_c64 names (no new symbol);
+                          * dhqr_factor_batched_pivoted_f64, dhqr_rank_batched_f64, dhqr_solve_batched_pivoted_f64,
+                          * dhqr_qr_batched_pivoted_f64, dhqr_lstsq_batched_f64 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -389,6 +391,65 @@ int32_t dhqr_form_r_batched_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int6
 int32_t dhqr_form_r_batched_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
                                 const float *dalpha, int64_t stride_alpha, float *dR, int64_t ldr, int64_t strideR,
                                 int64_t batch);
+
+/* ------------------------------------------------------- column-pivoted QR and rank-revealing least squares: batches, Float64
+ * The entry points above assume full column rank: a zero column gives a NaN reflector, a nearly collinear design matrix a
+ * huge, meaningless x.  These factor with COLUMN PIVOTING, A_k P_k = Q_k R_k (LAPACK geqp3's ordering), estimate the rank from
+ * the diagonal of R and solve min ||A_k x - b|| with the columns behind the rank dropped (gelsy's basic solution).  The
+ * reference has no counterpart.  Strided like the batched blocks above; jpvt_k (n int32) at djpvt + k*stride_jpvt.  The
+ * factor format is the one at the top of this file plus the permutation, so a pivoted factor is a valid argument of
+ * dhqr_apply_q_batched_f64, dhqr_form_q_batched_f64 and dhqr_form_r_batched_f64: they give Q_k, R_k with
+ * A_k[:, jpvt_k] = Q_k R_k.  Device-resident and asynchronous on the context's stream unless stated otherwise.
+ *   dhqr_factor_batched_pivoted_f64  in place; jpvt_k[j] (0-based) is the original column now in position j.  Step j: the
+ *                            squared 2-norms of rows >= j of the columns j .. n-1 are computed afresh from the working matrix
+ *                            in double (no downdating); the smallest column that attains the maximum is taken (compared with
+ *                            `>`: a NaN never wins) and swapped with column j in whole, R rows included.  The reflector is
+ *                            formed as dhqr_factor_batched_f64 forms it, except that a pivot entry of exactly 0 takes
+ *                            alpha = -norm (alphafactor(0) = -1) and so a valid reflector.  A maximum of exactly 0: the rest
+ *                            is zero, every remaining column c gets alpha_c = 0 and v_c = sqrt(2) e_c, no more swaps.  A
+ *                            finite matrix in range therefore always gets a finite factor, and |alpha_j| does not increase
+ *                            with j; a non-finite matrix keeps its trouble to itself and jpvt stays a permutation.
+ *                            RANGE: the pivot search is NOT scaled -- entries must be 0 or of magnitude within
+ *                            [1e-150, 1e150].
+ *   dhqr_rank_batched_f64    drank[k] (int32) <- the number of leading j with |alpha_j| > rc |alpha_0|, counting stops at
+ *                            the first failure (a NaN stops it; a zero matrix has rank 0); rc = rcond if rcond >= 0, else
+ *                            max(m, n) 2^-52.  One element-wise launch; not counted by the profile.
+ *   dhqr_solve_batched_pivoted_f64  with r = clamp(drank[k], 0, n): dB_k (m x nrhs) <- [z; tail], what solve_householder!
+ *                            leaves when run with the first r columns of the factor: z = R11^-1 (Q_r' B_k)[0:r], and rows
+ *                            r .. m-1 hold the part of B_k outside the range of A_k -- the 2-norm of those rows of a column is
+ *                            its residual ||A_k x - b||.  dX_k (n x nrhs, ldx) <- the basic solution: x[jpvt[i]] = z_i for
+ *                            i < r, exact zeros elsewhere.  r = 0: dB_k is left untouched, X_k = 0.
+ *   dhqr_qr_batched_pivoted_f64  host in / host out form of the factorisation; synchronous.
+ *   dhqr_lstsq_batched_f64   host in / host out: factors a staged copy, computes the ranks, solves, copies hX_k (n x nrhs) and
+ *                            hrank[k] out; hA and hB are not modified; synchronous.  Both host forms stage through the buffer
+ *                            of dhqr_qr_batched_f64 (dhqr_trim releases it).
+ * Routes:
+ *   m <= 64 and n <= 32      (small route on) ONE launch per call, one WAVE per matrix (csrc/dhqr_batched_pivoted.h): the
+ *                            kernels of dhqr_factor_batched_f64 / dhqr_solve_batched_f64 with the pivot step / with the
+ *                            wave's own rank in place of n.  The pivoted factor of A has the BITS of dhqr_factor_batched_f64
+ *                            on A[:, jpvt] (where no pivot entry is exactly 0); dB after the solve has the bits of
+ *                            dhqr_solve_batched_f64 called with n = r on that factor, column by column, whatever nrhs, the
+ *                            column's place and the batch.
+ *   every other shape        (and every shape with the small route off) ONE launch per call, one workgroup per matrix
+ *                            (factor) or per (matrix, column of B) (solve), in place in device memory, in plain double but
+ *                            for the reflector's norm.  This tier exists for completeness -- any shape gets an answer --,
+ *                            not for speed.
+ * With profiling on a factor counts ONE n_rank1 group and a solve ONE n_solve group per launch.
+ * batch == 0, n == 0 or nrhs == 0: no-op, DHQR_OK.  DHQR_EINVAL (nothing is written): what the batched family rejects, a null
+ * jpvt, rank or X, stride_jpvt < n, ldx < n, strideX < ldx*(nrhs-1) + n; off the wave tier batch * nrhs > 2^31 - 1. */
+int32_t dhqr_factor_batched_pivoted_f64(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                        double *dalpha, int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_rank_batched_f64(dhqr_ctx *ctx, const double *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond,
+                              int32_t *drank, int64_t batch);
+int32_t dhqr_solve_batched_pivoted_f64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                       const double *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
+                                       const int32_t *drank, double *dB, int64_t nrhs, int64_t ldb, int64_t strideB, double *dX,
+                                       int64_t ldx, int64_t strideX, int64_t batch);
+int32_t dhqr_qr_batched_pivoted_f64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
+                                    int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_lstsq_batched_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *hB,
+                               int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, double *hX, int64_t ldx, int64_t strideX,
+                               int32_t *hrank, int64_t batch);
 
 /* KAT hook mirroring partialdot(a, b, lo:hi, Float64) (src:42-49; test/partialdot.jl:18):
  * sum_{i=lo}^{hi-1} da[i]*db[i] (0-based, hi exclusive) reduced on the device with the same

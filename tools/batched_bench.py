@@ -31,6 +31,12 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
                                                            caller had before: a loop of dhqr_apply_q_f64, one call per matrix
                                                            (on the first LOOP_BATCH matrices, scaled per matrix); ROUNDS
                                                            rounds of 10 repetitions each, every round's median listed
+       --pivot [--shapes ...] [--batches 16384]            what column pivoting costs: dhqr_factor_batched_pivoted_f64 +
+                                                           dhqr_rank_batched_f64 + dhqr_solve_batched_pivoted_f64 (one
+                                                           right-hand side) against dhqr_factor_batched_f64 +
+                                                           dhqr_solve_batched_f64 on the same resident data, at PIVOT_SHAPES
+                                                           with batch 16384 unless told otherwise; ROUNDS rounds of 10
+                                                           repetitions, every round's median, and the factors alone
 
 Per point: 3 warm-up and 10 timed repetitions of (restore the inputs, synchronise, START, calls, synchronise, STOP) on the
 host clock -- a caller's view, launch costs included; median and min-max of matrices per second; the ratio batched / looped
@@ -454,6 +460,108 @@ def main_applyq(a, shapes, batches):
     return rc
 
 
+PIVOT_SHAPES = [(16, 8), (40, 17), (64, 32)]
+
+
+def point_pivot(m, n, batch):
+    """one point of --pivot: pivoted (factor + rank + truncated solve) and unpivoted (factor + solve) on the same inputs --
+    the project's generator with column c scaled by 1 + 0.25 c, full rank --, and each factor alone"""
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as g
+    pkg = g.import_package()
+    os.environ["DHQR_SMALL"] = "1"
+    A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0")
+    A0 *= 1.0 + 0.25 * torch.arange(n, dtype=torch.float64, device="cuda:0")
+    b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    A, b = A0.clone(), b0.clone()
+    al = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    jp = torch.zeros((batch, n), dtype=torch.int32, device="cuda:0")
+    rk = torch.zeros((batch,), dtype=torch.int32, device="cuda:0")
+    x = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    L, P, chk = pkg._lib.lib(), ctypes.c_void_p, pkg._lib.check
+    pa, pal, pb, pjp, prk, px = (P(t.data_ptr()) for t in (A, al, b, jp, rk, x))
+    ctx = pkg.Context(0)
+    h = ctx.handle
+
+    def f_piv():
+        chk(L.dhqr_factor_batched_pivoted_f64(h, pa, m, n, m, m * n, pal, n, pjp, n, batch))
+
+    def f_plain():
+        chk(L.dhqr_factor_batched_f64(h, pa, m, n, m, m * n, pal, n, batch, 0))
+
+    def pivoted():
+        f_piv()
+        chk(L.dhqr_rank_batched_f64(h, pal, m, n, n, -1.0, prk, batch))
+        chk(L.dhqr_solve_batched_pivoted_f64(h, pa, m, n, m, m * n, pal, n, pjp, n, prk, pb, 1, m, m, px, n, n, batch))
+
+    def plain():
+        f_plain()
+        chk(L.dhqr_solve_batched_f64(h, pa, m, n, m, m * n, pal, n, pb, m, batch))
+
+    def measure(fn):
+        rates = []
+        for r in range(WARMUP + REPS):
+            A.copy_(A0)
+            b.copy_(b0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            dt = time.perf_counter() - t0
+            if r >= WARMUP:
+                rates.append(batch / dt)
+        return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
+
+    out = {"m": m, "n": n, "batch": batch, "pivoted": [], "plain": [], "factor_pivoted": [], "factor_plain": []}
+    for _ in range(ROUNDS):
+        out["pivoted"].append(measure(pivoted))
+        xp = x.clone()
+        out["plain"].append(measure(plain))
+        xu = b[:, :n].clone()
+        out["factor_pivoted"].append(measure(f_piv))
+        out["factor_plain"].append(measure(f_plain))
+    assert int(rk.min()) == n, "the inputs were meant to have full rank"
+    assert ((xp - xu).abs().amax(dim=1) <= 1e-9 * xp.abs().amax(dim=1)).all(), "pivoted and unpivoted solutions differ"
+    ctx.close()
+    print("POINT " + json.dumps(out), flush=True)
+
+
+def main_pivot(a, shapes, batches):
+    lines = [f"# tools/batched_bench.py --pivot: matrices per second, {ROUNDS} rounds of {REPS} repetitions in one process, every round's median, then min .. max over all repetitions",
+             "# pivoted = dhqr_factor_batched_pivoted_f64 + dhqr_rank_batched_f64 + dhqr_solve_batched_pivoted_f64 (one right-hand side, X written);",
+             "# unpivoted = dhqr_factor_batched_f64 + dhqr_solve_batched_f64; the same resident full-rank inputs; `factors` = the two factor calls alone"]
+    print("\n".join(lines), flush=True)
+    rc = 0
+    for (m, n) in shapes:
+        for batch in batches:
+            p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
+                                str(m), str(n), str(batch), "--pivot"], capture_output=True, text=True)
+            row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
+            if p.returncode != 0 or not row:
+                lines.append(f"{m}x{n} batch {batch}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
+                print(lines[-1], flush=True)
+                rc = 1
+                break
+            r = json.loads(row[0][6:])
+            med = lambda rs: statistics.median(v["median"] for v in rs)
+            rounds = lambda rs: " ".join(f"{v['median']:.0f}" for v in rs) + f" ({min(v['min'] for v in rs):.0f} .. {max(v['max'] for v in rs):.0f})"
+            ratios = " ".join("%.3f" % (x["median"] / y["median"]) for x, y in zip(r["pivoted"], r["plain"]))
+            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} | pivoted {rounds(r['pivoted'])} | unpivoted {rounds(r['plain'])} | "
+                   f"pivoted/unpivoted per round {ratios} | "
+                   f"median {med(r['pivoted']) / med(r['plain']):5.2f}x | factors: pivoted {med(r['factor_pivoted']):.0f} unpivoted "
+                   f"{med(r['factor_plain']):.0f} ratio {med(r['factor_pivoted']) / med(r['factor_plain']):5.2f}x")
+            lines.append(txt)
+            print(txt, flush=True)
+        if rc:
+            break
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return rc
+
+
 def fmt(r):
     return f"{r['median']:12.0f} ({r['min']:.0f} .. {r['max']:.0f})"
 
@@ -512,10 +620,13 @@ def main():
     ap.add_argument("--applyq", choices=("t", "n", "q"), default=None, help="Q'B, QB or the explicit Q of a resident batched factor")
     ap.add_argument("--batches", default=None, help="e.g. 16384 or 64,1024 (default: every batch of BATCHES)")
     ap.add_argument("--arm", choices=("s", "t", "n", "q"), default=None, help="(what main_arms runs in a child: one arm of one point)")
+    ap.add_argument("--pivot", action="store_true", help="column-pivoted factor + rank + truncated solve against the unpivoted factor + solve")
     ap.add_argument("--limit", type=int, default=300, help="seconds per point (timeout -k 10)")
     a = ap.parse_args()
     if a.point:
-        if a.arm is not None:
+        if a.pivot:
+            point_pivot(*a.point)
+        elif a.arm is not None:
             point_arm(*a.point, a.nrhs or 16, a.arm)
         elif a.applyq is not None:
             point_applyq(*a.point, a.nrhs or 16, a.applyq, a.dtype)
@@ -527,6 +638,8 @@ def main():
     t = a.dtype
     shapes = (C64_SHAPES if t == "c64" else SHAPES) if a.shapes is None else [tuple(int(v) for v in sh.split("x")) for sh in a.shapes.split(",")]
     batches = (C64_BATCHES if t == "c64" else BATCHES) if a.batches is None else [int(v) for v in a.batches.split(",")]
+    if a.pivot:
+        return main_pivot(a, PIVOT_SHAPES if a.shapes is None else shapes, batches if a.batches is not None else [16384])
     if t == "c64" and (a.applyq is not None or a.nrhs is not None) and all(small_tier(m, n) for m, n in shapes):
         return main_arms(a, shapes, batches if a.batches is not None else [16384])
     if a.applyq is not None:
