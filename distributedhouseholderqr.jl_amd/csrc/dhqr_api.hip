@@ -2043,7 +2043,7 @@ int32_t dhqr_ldiv_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64
 
 // ---- batches of small matrices, Float32, several right-hand sides per matrix (dhqr.h: dhqr_factor_batched_f64 ...) -------
 // The host side -- argument rules, tiers, staging -- is dhqr_batched_host.h, once for both element types; the kernels are
-// dhqr_batched.h, dhqr_f32.h, dhqr_batched_nrhs.h, dhqr_batched_applyq.h and dhqr_small.h.
+// dhqr_wave.h, dhqr_batched.h, dhqr_batched_nrhs.h, dhqr_batched_applyq.h and dhqr_small.h.
 int32_t dhqr_factor_batched_f64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
                                 int64_t stride_alpha, int64_t batch, int32_t nb) {
   ENTER(c);

@@ -2,30 +2,27 @@
 // matrices: one WAVE per matrix.
 //
 // k_batched_applyq_wave / k_batched_applyq_wave_s are k_batched_ldiv_wave_nrhs / _s (dhqr_batched_nrhs.h) without the back
-// substitution: same shapes (m <= 64, n <= NC = 8, 16 or 32), same launch geometry (BQW_WAVES matrices per workgroup, lane l
-// on row l), same launch bounds, no LDS, no barrier, no wait of any kind.  The factor is loaded ONCE into registers -- no
-// alpha: Q is made of the reflectors alone --, and the columns of B_k walk past it in groups of RG (BQA_RG_D, BQN_RG), the
-// body unrolled over the group, the group's chains side by side.
+// substitution, under the same launch geometry and launch bounds, and like them the written-out form of the steps of
+// dhqr_wave.h: built from bqw_reflect_group the Float64 kernel moved the SIGN of the NaNs a NaN reflector leaves in its matrix
+// (profiles/wave_tier_refactor.txt), and a byte is a byte.  Whoever changes a step there changes it here.  The factor is loaded
+// ONCE into registers -- no alpha: Q is made of the reflectors alone --, and the columns of B_k walk past it in groups of RG
+// (bqa_rg).
 //
-//   TRANS = 1   B <- Q'B: reflectors left to right (src:215-224).  Per column exactly the expressions of the Q'B phase of
-//               k_batched_ldiv_wave_nrhs(_s), in the same order, so rows n .. m-1 of the result have the BITS of the same rows
-//               of what the solve leaves in B (the tail of Q'B, which back substitution never touches).
-//   TRANS = 0   B <- QB: the same per-reflector expressions, reflectors right to left, c = n-1 .. 0.
+//   TRANS = 1   B <- Q'B: reflectors left to right (src:215-224).  Per column the reflector step of the solve in the same
+//               order, so rows n .. m-1 of the result have the BITS of the same rows of what the solve leaves in B (the tail
+//               of Q'B, which back substitution never touches).
+//   TRANS = 0   B <- QB: the same step, reflectors right to left, c = n-1 .. 0.
 //   FORMQ       TRANS = 0 on columns e_r generated in registers: B is the m x n Q_k, of which nothing is read and all m rows
 //               of the n columns are written.  Column r is H_0 ... H_r e_r: the reflectors c > r act as the identity on e_r
 //               (v_c is zero above row c, e_r below row r: the dot product is an exact zero), so a group skips the
 //               reflectors behind its last column under one wave-uniform branch.  For a finite factor the result compares
 //               equal to TRANS = 0 applied to [I; 0].
 //
-// Float64 carries a column in double-double (dd_add_prod, wave_sum_dd_plain) and stores hi + lo; the low part is folded into
-// the high one (dd_renorm) after every eighth reflector and once at the end.  TRANS = 1: after c = 7, 15, 23, as the solve
-// does.  TRANS = 0: after c = 24, 16, 8 -- by the reflector's INDEX, not by how many this column has seen, so at most eight
-// reflectors lie between two renormalisations wherever the walk starts (n - 1, or the group's last column under FORMQ) and
-// FORMQ renormalises exactly where TRANS = 0 on [I; 0] does.  Float32 carries a column in plain double and rounds once.
-// Column r of the result depends neither on nrhs nor on its place in its group nor on the batch.
-//
-// Column r of matrix k lives at B + k strideB + r ldb and is read and written in place, one coalesced access per column.  A
-// tail group of 1 .. RG-1 columns loads zeros for the missing columns and stores nothing for them.
+// Float64 renormalises a column after every eighth reflector and once at the end.  TRANS = 1: after c = 7, 15, 23, as the
+// solve does.  TRANS = 0: after c = 24, 16, 8 -- by the reflector's INDEX, not by how many this column has seen, so at most
+// eight reflectors lie between two renormalisations wherever the walk starts (n - 1, or the group's last column under FORMQ)
+// and FORMQ renormalises exactly where TRANS = 0 on [I; 0] does.  Column r of the result depends neither on nrhs nor on its
+// place in its group nor on the batch.
 //
 // k_batched_form_r: R_k (n x n) = the strict upper part of H_k, alpha_k on the diagonal, zeros written below (src:296-309);
 // k_batched_eye: [I; 0], the input of the explicit Q beyond the wave tier.  Plain element-wise kernels for every shape and
@@ -34,11 +31,7 @@
 #include <type_traits>
 #include "dhqr_batched_nrhs.h"
 
-// Float64 columns per group.  Without alpha and 1 / alpha beside the matrix, NC = 16 holds four double-double chains under
-// the launch bound where the solve holds three (BQN_RG_D); NC = 32 stays at three (profiles/batched_kernel_resources.txt).
-#define BQA_RG_D(NC_) ((NC_) <= 16 ? BQN_RG : 3)
-
-template <int NC, int TRANS, int FORMQ = 0, int RG = BQA_RG_D(NC)>
+template <int NC, int TRANS, int FORMQ = 0, int RG = bqa_rg<double>(NC)>
 __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_applyq_wave(
     const double *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, double *__restrict__ B, int nrhs, int64_t ldb,
     int64_t strideB, int64_t batch) {
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_a
 }
 
 // the Float32 method: the matrix in float, a column in plain double, rounded once at the end
-template <int NC, int TRANS, int FORMQ = 0, int RG = BQN_RG>
+template <int NC, int TRANS, int FORMQ = 0, int RG = bqa_rg<float>(NC)>
 __global__ __launch_bounds__(64 * BQW_WAVES, BQS_MIN_WAVES(NC)) void k_batched_applyq_wave_s(
     const float *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, float *__restrict__ B, int nrhs, int64_t ldb,
     int64_t strideB, int64_t batch) {

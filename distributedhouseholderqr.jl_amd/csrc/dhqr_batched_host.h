@@ -5,7 +5,7 @@
 // functions themselves: ENTER, the argument check, one call into this file.
 // Tiers by shape.  Float64: one wave per matrix (dhqr_batched.h) | the single-workgroup kernels of dhqr_small.h with grid =
 // batch, in their barrier form | a host loop over the single-matrix drivers.  Float32: m <= 64 and n <= 32 with the small
-// route on -- one launch of the wave-per-matrix kernels of dhqr_f32.h (a single matrix is a batch of 1) --, everything else
+// route on -- one launch of the same wave-per-matrix kernels with T = float (a single matrix is a batch of 1) --, everything else
 // PROMOTED: widened into a Float64 workspace of the context, the Float64 route with the caller's nb, rounded back.
 // ComplexF64 (dhqr_factor_batched_c64 ... dhqr_ldiv_batched_c64): the wave tier -- one launch of the kernels of
 // dhqr_batched_complex.h -- | up to 128 rows one launch of the single-workgroup kernels of dhqr_small_complex.h with grid =
@@ -127,18 +127,14 @@ static inline int wave_nc(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : 32; }
 // right-hand sides per group of the multi-column kernels (dhqr_batched_nrhs.h) in the instantiation NC
 template <typename T>
 static inline int wave_rg(int NC) {
-  if constexpr (std::is_same_v<T, double>) return BQN_RG_D(NC);
-  else return BQN_RG;
+  return bqn_rg<T>(NC);
 }
 
 template <typename T>
 static int32_t wave_factor(dhqr_ctx *c, T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dalpha, int64_t stride_alpha,
                            int64_t batch) {
   CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
-  if constexpr (std::is_same_v<T, double>)
-    WAVE_LAUNCH(k_batched_qr_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
-  else
-    WAVE_LAUNCH(k_batched_qr_wave_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
+  WAVE_LAUNCH_T(k_batched_qr_wave, WAVE_TARGS(T), n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, batch);
   if (c->profiling)  // (an element update reads and writes one T)
     for (int64_t j = 0; j + 1 < n; ++j)
       c->st.bytes_rank1 += (double)batch * (double)(2 * sizeof(T)) * (double)(m - j) * (double)(n - j - 1);
@@ -148,10 +144,7 @@ template <typename T>
 static int32_t wave_solve(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *dalpha,
                           int64_t stride_alpha, T *db, int64_t strideb, int64_t batch) {
   CHECK(prof_begin(c, CAT_SOLVE));
-  if constexpr (std::is_same_v<T, double>)
-    WAVE_LAUNCH(k_batched_ldiv_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
-  else
-    WAVE_LAUNCH(k_batched_ldiv_wave_s, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
+  WAVE_LAUNCH_T(k_batched_ldiv_wave, WAVE_TARGS(T), n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, db, strideb, batch);
   return prof_end(c);
 }
 // several right-hand sides per matrix: ONE launch of the multi-column kernels of dhqr_batched_nrhs.h
@@ -159,6 +152,7 @@ template <typename T>
 static int32_t wave_solve_nrhs(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *dalpha,
                                int64_t stride_alpha, T *dB, int64_t nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
   CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
+  // (the real kernels are two: dhqr_batched_nrhs.h says why they are not one template over T)
   if constexpr (std::is_same_v<T, double>)
     WAVE_LAUNCH(k_batched_ldiv_wave_nrhs, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, dB, (int)nrhs, ldb, strideB, batch);
   else if constexpr (std::is_same_v<T, double2>)

@@ -1,45 +1,24 @@
-// dhqr_batched_nrhs.h -- H_k \ B_k for a BATCH of tiny matrices with SEVERAL right-hand sides each: one WAVE per matrix.
+// dhqr_batched_nrhs.h -- H_k \ B_k for a BATCH of tiny matrices with SEVERAL right-hand sides each, Float64 and Float32: one
+// WAVE per matrix (dhqr_wave.h), the launch geometry and launch bounds of k_batched_ldiv_wave (dhqr_batched.h).
 //
-// k_batched_ldiv_wave_nrhs / k_batched_ldiv_wave_nrhs_s are the multi-column forms of k_batched_ldiv_wave (dhqr_batched.h)
-// and k_batched_ldiv_wave_s (dhqr_f32.h): same shapes (m <= 64, n <= NC = 8, 16 or 32), same launch geometry (BQW_WAVES
-// matrices per workgroup, lane l on row l), same launch bounds, no LDS, no barrier, no wait of any kind.  Local fits and
-// per-pixel regressions solve several channels against one small design matrix; looping the single-column kernel over the
-// channels re-reads every matrix once per channel.  Here the factor and alpha are loaded ONCE into registers, and the
-// right-hand sides walk past them: a runtime loop over groups of RG columns of B_k (BQN_RG = 4; BQN_RG_D), the body unrolled
-// over the group.  The RG Q'b chains of a group -- each a serial DPP reduction per reflector -- are independent and
-// interleave, the way the four column dots of a trailing-update group do in k_batched_qr_wave.
+// Local fits and per-pixel regressions solve several channels against one small design matrix; looping the single-column
+// kernel over the channels re-reads every matrix once per channel.  Here the factor and alpha are loaded ONCE into registers,
+// and the right-hand sides walk past them: a runtime loop over groups of RG columns of B_k (bqn_rg), the body unrolled over
+// the group.  Column r of matrix k lives at B + k strideB + r ldb and is read and written in place ([X_k; tail of Q'B_k]).
 //
-// Column r of matrix k lives at B + k strideB + r ldb and is read and written in place ([X_k; tail of Q'B_k]), one
-// coalesced access per column.  A tail group of 1 .. RG-1 columns loads zeros for the missing columns and stores nothing
-// for them.
+// Per column these are the expressions of k_batched_ldiv_wave in the same order, so column r of the result is BIT-IDENTICAL
+// to what the single-column kernel returns for that column alone: it depends neither on nrhs nor on the column's position in
+// its group nor on the batch.
 //
-// Arithmetic: per column, the expressions of the single-column kernel in the same order -- Float64 carries b in
-// double-double (dd_add_prod, wave_sum_dd_plain, dd_renorm after every eighth reflector and once at the end, the
-// reciprocal-plus-one-correction division), Float32 carries b in plain double and rounds once at the end.  So column r of
-// the result is BIT-IDENTICAL to what the single-column kernel returns for that column alone: it depends neither on nrhs
-// nor on the column's position in its group nor on the batch.
+// These two kernels are NOT built from the steps of dhqr_wave.h (bqw_load, bqw_reflect_group, bqw_backsub_group), of which
+// they are the written-out form: built from them they compute the same bits but
+// allocate other registers (profiles/wave_tier_refactor.txt: Float64 NC = 8 two scalar registers fewer; Float32 34 / 43 / 61
+// vector registers instead of 40 / 45 / 62).  Whoever changes a step there changes it here.
 #pragma once
 #include "dhqr_f32.h"
 
-#define BQN_RG 4  // right-hand sides per group
-// Float64, NC = 16 and 32: three.  A group of four double-double chains beside 2 NC registers of matrix does not fit under
-// the launch bound there (NC = 16: 2 registers spilled at 80; NC = 32: the matrix itself in scratch memory, 272 bytes), a
-// group of three does without scratch (profiles/batched_kernel_resources.txt).
-#define BQN_RG_D(NC_) ((NC_) <= 8 ? BQN_RG : 3)
-// The factor, alpha and 1 / alpha do not change from group to group, so the compiler would move everything derived from them
-// and from the lane number -- the masked reflectors v_c, the negated and widened R columns, 4 NC scalar registers of broadcast
-// alphas, 6 NC of lane masks -- in front of the group loop: a second and third copy of the matrix in registers, and scratch
-// memory.  An empty statement that claims to modify the register keeps each derivation inside the loop body, where it lives
-// for one reflector.  (No instruction.  What the compiler does with it depends on its version: after a ROCm upgrade re-read
-// the kernels' scratch sizes, profiles/batched_kernel_resources.txt says how; they must stay 0.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BQN_KEEP_IN_LOOP(x_) asm volatile("" : "+v"(x_))
-#else
-#define BQN_KEEP_IN_LOOP(x_) ((void)0)
-#endif
-
 // solve_householder!(B_k[:, r], H_k, alpha_k) (src:284-294) for r < nrhs, k < batch: B_k = B + k strideB (m x nrhs, ldb).
-template <int NC, int RG = BQN_RG_D(NC)>
+template <int NC, int RG = bqn_rg<double>(NC)>
 __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_ldiv_wave_nrhs(
     const double *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, const double *__restrict__ alpha, int64_t stride_alpha,
     double *__restrict__ B, int nrhs, int64_t ldb, int64_t strideB, int64_t batch) {
@@ -123,8 +102,8 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_l
   }
 }
 
-// the Float32 method: the matrix in float, b in plain double, rounded once at the end (k_batched_ldiv_wave_s)
-template <int NC, int RG = BQN_RG>
+// the Float32 method: the matrix in float, b in plain double, rounded once at the end (k_batched_ldiv_wave<NC, float>)
+template <int NC, int RG = bqn_rg<float>(NC)>
 __global__ __launch_bounds__(64 * BQW_WAVES, BQS_MIN_WAVES(NC)) void k_batched_ldiv_wave_nrhs_s(
     const float *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, const float *__restrict__ alpha, int64_t stride_alpha,
     float *__restrict__ B, int nrhs, int64_t ldb, int64_t strideB, int64_t batch) {

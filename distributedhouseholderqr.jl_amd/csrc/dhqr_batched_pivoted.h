@@ -40,18 +40,12 @@ template <int NC>
 __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_qrp_wave(double *__restrict__ A, int64_t lda, int64_t strideA, int m,
                                                                      int n, double *__restrict__ alpha, int64_t stride_alpha,
                                                                      int32_t *__restrict__ jpvt, int64_t stride_jpvt, int64_t batch) {
-  static_assert(NC % 4 == 0 && NC <= BQW_MAX_N, "columns in groups of four");
-  const int l = threadIdx.x & 63;
-  const int64_t k = (int64_t)blockIdx.x * BQW_WAVES + (threadIdx.x >> 6);
+  const int l = bqw_lane();
+  const int64_t k = bqw_matrix();
   if (k >= batch) return;  // (the whole wave)
   double *Ak = A + k * strideA;
   double a[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const bool in = c < n && l < m;  // (no branch: every load of the matrix is in flight before the first use)
-    const double t = Ak[in ? (int64_t)l + (int64_t)c * lda : 0];
-    a[c] = in ? t : 0.0;
-  }
+  bqw_load(a, Ak, lda, m, n, l);
   double alv = 0.0;  // lane j keeps alpha_j
   int jp = l;        // lane c keeps jpvt[c]
   int jz = n;        // the first column of the zero tail
@@ -100,22 +94,11 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_q
       jp = l == j ? pp : (l == p ? pj : jp);
     }
     // reflector j (src:129-140): rows >= m hold zeros
-    dhqr_dd acc = {0.0, 0.0};
-    dd_add_sq(acc, l >= j ? x : 0.0);
-    const dhqr_dd ss = wave_sum_dd_plain(acc);
-    const double s2 = ss.hi + ss.lo;
+    const double s2 = bqw_norm2<double>(l >= j ? x : 0.0);
     const double h = smq_readlane(x, j);
-    double sn, f;
-    if (s2 > 0.0 && s2 < 1e300) {
-      double rinv, sq;
-      dhqr_sqrt_rsqrt(s2, sn, rinv);                 // src:129
-      dhqr_sqrt_rsqrt(fma(sn, fabs(h), s2), sq, f);  // src:131: s (s + |h|) = s^2 + s |h|
-    } else {
-      sn = sqrt(s2);
-      f = 1.0 / sqrt(sn * (sn + fabs(h)));
-    }
-    const double al = sn * dhqr_alphafactor_p(h);  // src:130
-    const double piv = (h - al) * f;               // src:132
+    double sn, f, al;
+    dhqr_reflector_scalars(s2, h, dhqr_alphafactor_p, sn, f, al);
+    const double piv = (h - al) * f;  // src:132
     const double v = l > j ? x * f : (l == j ? piv : 0.0);  // src:133-140
     if (l == j) alv = al;
     const double xv = l >= j ? v : x;  // rows < j keep R
@@ -130,25 +113,12 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_q
         for (int cc = 0; cc < 4; ++cc) a[4 * g + cc] = (cc == (j & 3)) ? xv : a[4 * g + cc];
       }
     }
-    // trailing update (src:198-213): columns >= n hold zeros and stay zeros
-#pragma unroll
-    for (int g = 0; g < NC / 4; ++g) {
-      if (4 * g + 3 > j && 4 * g < n) {
-        double d[4];
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) d[cc] = wave_sum_dpp(v * a[4 * g + cc]);  // src:42-49
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc)  // src:156-160, src:209: rows >= j of the columns behind j, nothing else
-          a[4 * g + cc] = (4 * g + cc > j && l >= j) ? fma(-v, d[cc], a[4 * g + cc]) : a[4 * g + cc];
-      }
-    }
+    bqw_trailing_update(a, v, j, n, l);
   }
   // the zero tail: alpha_c = 0 (alv is 0 in the lanes >= jz), v_c = sqrt(2) e_c for c >= jz
 #pragma unroll
   for (int c = 0; c < NC; ++c) a[c] = (c >= jz && c < n && l >= c) ? (l == c ? BQP_SQRT2 : 0.0) : a[c];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-    if (c < n && l < m) Ak[(int64_t)l + (int64_t)c * lda] = a[c];
+  bqw_store(a, Ak, lda, m, n, l);
   if (l < n) {
     alpha[k * stride_alpha + l] = alv;
     jpvt[k * stride_jpvt + l] = jp;
@@ -164,17 +134,11 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_l
     const double *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, const double *__restrict__ alpha, int64_t stride_alpha,
     const int32_t *__restrict__ jpvt, int64_t stride_jpvt, const int32_t *__restrict__ rank, double *__restrict__ B, int nrhs, int64_t ldb,
     int64_t strideB, double *__restrict__ X, int64_t ldx, int64_t strideX, int64_t batch) {
-  int l = threadIdx.x & 63;
-  const int64_t k = (int64_t)blockIdx.x * BQW_WAVES + (threadIdx.x >> 6);
+  int l = bqw_lane();
+  const int64_t k = bqw_matrix();
   if (k >= batch) return;  // (the whole wave)
-  const double *Ak = A + k * strideA;
   double a[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const bool in = c < n && l < m;
-    const double t = Ak[in ? (int64_t)l + (int64_t)c * lda : 0];
-    a[c] = in ? t : 0.0;
-  }
+  bqw_load(a, A + k * strideA, lda, m, n, l);
   const int rk = __builtin_amdgcn_readfirstlane(rank[k]);
   const int r = rk < 0 ? 0 : (rk > n ? n : rk);  // wave-uniform
   double al = l < r ? alpha[k * stride_alpha + l] : 1.0;  // lane j: alpha_j
@@ -182,47 +146,23 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_l
   double rinv = dhqr_rcp(al);
 #pragma unroll 1
   for (int q = 0; q < nrhs; ++q) {
-    // (what derives from the matrix, alpha and the lane number stays inside the loop: dhqr_batched_nrhs.h)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) BQN_KEEP_IN_LOOP(a[c]);
+    bqw_keep_in_loop(a);  // (BQN_KEEP_IN_LOOP, dhqr_wave.h)
     BQN_KEEP_IN_LOOP(al);
     BQN_KEEP_IN_LOOP(rinv);
     BQN_KEEP_IN_LOOP(l);
     double *bk = B + k * strideB + (int64_t)q * ldb;
-    dhqr_dd bb;
-    bb.hi = l < m ? bk[l] : 0.0;
-    bb.lo = 0.0;
+    dhqr_dd bb[1];
+    bqw_col_set(bb[0], l < m ? bk[l] : 0.0);
     // ---- b <- Q_r'b: reflectors left to right (src:215-224)
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      if (c < r) {  // (wave-uniform)
-        const double v = l >= c ? a[c] : 0.0;  // rows < c of a factored column hold R
-        dhqr_dd p = {0.0, 0.0};
-        dd_add_prod(p, v, bb.hi);  // src:217: v_i b_i, b_i = hi + lo
-        p.lo = fma(v, bb.lo, p.lo);
-        const dhqr_dd sd = wave_sum_dd_plain(p);
-        const double s = sd.hi + sd.lo;
-        dd_add_prod(bb, -s, v);  // src:218-220: b_i -= v_i s
-        if ((c & 7) == 7) dd_renorm(bb);  // the low part stays small against the high one
-      }
-    }
-    dd_renorm(bb);
+    for (int c = 0; c < NC; ++c)
+      if (c < r) bqw_reflect_group(bqw_reflector(a, c, l), bb, (c & 7) == 7);  // (wave-uniform)
+    bqw_col_renorm(bb);
     // ---- back substitution on R11, columns right to left (src:244-254)
 #pragma unroll
-    for (int c = NC - 1; c >= 0; --c) {
-      if (c < r) {
-        const double bq = smq_readlane(bb.hi + bb.lo, c), aj = smq_readlane(al, c), ri = smq_readlane(rinv, c);
-        double xj = bq * ri;
-        xj = fma(fma(-aj, xj, bq), ri, xj);
-        if (l == c) {
-          bb.hi = xj;
-          bb.lo = 0.0;
-        } else if (l < c) {
-          dd_add_prod(bb, -a[c], xj);  // src:248-250
-        }
-      }
-    }
-    const double z = bb.hi + bb.lo;
+    for (int c = NC - 1; c >= 0; --c)
+      if (c < r) bqw_backsub_group(c, l, a[c], al, rinv, bb);
+    const double z = bqw_col_value(bb[0]);
     if (r > 0 && l < m) bk[l] = z;
     // jpvt is a permutation: every entry of the column is written once (an index out of range is not written at all)
     if (l < n && jp >= 0 && jp < n) X[k * strideX + (int64_t)q * ldx + jp] = l < r ? z : 0.0;
@@ -316,17 +256,9 @@ __global__ __launch_bounds__(BQPG_THREADS) void k_batched_qrp_general(double *__
     for (int64_t i = j + t; i < m; i += BQPG_THREADS) dd_add_sq(acc, vj[i]);
     const double s2 = dd_block_sum<BQPG_THREADS>(acc, red);
     const double h = vj[j];
-    double sn, f;
-    if (s2 > 0.0 && s2 < 1e300) {
-      double rinv, sq;
-      dhqr_sqrt_rsqrt(s2, sn, rinv);                 // src:129
-      dhqr_sqrt_rsqrt(fma(sn, fabs(h), s2), sq, f);  // src:131
-    } else {
-      sn = sqrt(s2);
-      f = 1.0 / sqrt(sn * (sn + fabs(h)));
-    }
-    const double al = sn * dhqr_alphafactor_p(h);  // src:130
-    const double piv = (h - al) * f;               // src:132
+    double sn, f, al;
+    dhqr_reflector_scalars(s2, h, dhqr_alphafactor_p, sn, f, al);
+    const double piv = (h - al) * f;  // src:132
     __syncthreads();  // every thread has read h
     for (int64_t i = j + t; i < m; i += BQPG_THREADS) vj[i] = i == j ? piv : vj[i] * f;  // src:133-140
     if (t == 0) alk[j] = al;

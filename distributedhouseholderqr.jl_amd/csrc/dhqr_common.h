@@ -227,6 +227,21 @@ __device__ __forceinline__ double dhqr_rcp(double x) {
 __device__ __forceinline__ double dhqr_alphafactor(double x) {
   return x > 0.0 ? -1.0 : (x < 0.0 ? 1.0 : -x);
 }
+// The scalars of a real reflector from s2 = sum x_i^2 over the column, its pivot entry h and the route's alphafactor:
+// sn = ||x|| (src:129), f = 1 / sqrt(sn (sn + |h|)) (src:131), alpha = sn alphafactor(h) (src:130).  The caller forms the
+// pivot entry (h - alpha) f (src:132) where it stores it.  The second branch takes s2 = 0, an s2 whose product below would
+// overflow, inf and NaN.
+__device__ __forceinline__ void dhqr_reflector_scalars(double s2, double h, double (*alphafactor)(double), double &sn, double &f, double &al) {
+  if (s2 > 0.0 && s2 < 1e300) {
+    double rinv, sq;
+    dhqr_sqrt_rsqrt(s2, sn, rinv);
+    dhqr_sqrt_rsqrt(fma(sn, fabs(h), s2), sq, f);  // s (s + |h|) = s^2 + s |h|
+  } else {
+    sn = sqrt(s2);
+    f = 1.0 / sqrt(sn * (sn + fabs(h)));
+  }
+  al = sn * alphafactor(h);
+}
 
 // ---- inter-workgroup hand-over flags of the column pipelines (k_zpanel_pipe, rankk_lead_pipe) ----------------------
 // One array of 128 flags (one 128-byte line each) + one error word per context.  A flag holds the number (epoch) of the

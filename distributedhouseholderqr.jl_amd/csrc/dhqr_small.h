@@ -304,17 +304,9 @@ __global__ __launch_bounds__(EXTRA ? SMB_THREADS : SMQ_THREADS) void k_small_qr_
     // (the squares and the per-lane sums in double-double, the tree across the lanes in plain double: see wave_sum_dd_plain)
     const dhqr_dd ss = wave_sum_dd_plain(acc);
     const double s2 = ss.hi + ss.lo;
-    double sn, f;
-    if (s2 > 0.0 && s2 < 1e300) {
-      double rinv, sq;
-      dhqr_sqrt_rsqrt(s2, sn, rinv);                 // src:129
-      dhqr_sqrt_rsqrt(fma(sn, fabs(h), s2), sq, f);  // src:131: s (s + |h|) = s^2 + s |h|
-    } else {
-      sn = sqrt(s2);
-      f = 1.0 / sqrt(sn * (sn + fabs(h)));
-    }
-    const double al = sn * dhqr_alphafactor(h);      // src:130
-    const double piv = (h - al) * f;                 // src:132
+    double sn, f, al;
+    dhqr_reflector_scalars(s2, h, dhqr_alphafactor, sn, f, al);  // src:129-131
+    const double piv = (h - al) * f;                             // src:132
     double *vo = vb[jn & BM];
 #pragma unroll
     for (int r = 0; r < RBL; ++r) {

@@ -251,7 +251,7 @@ int32_t dhqr_ldiv_batched_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_
  * conventions, error codes (DHQR_EINVAL conditions, the n == 0 and batch == 0 no-ops) and factor format, in Float32.  Device
  * pointers need 4-byte alignment only.
  * Routes by shape, in this order:
- *   m <= 64 and n <= 32      NATIVE: one launch, one WAVE per matrix (csrc/dhqr_f32.h; a single matrix is a batch of 1).  The
+ *   m <= 64 and n <= 32      NATIVE: one launch, one WAVE per matrix (csrc/dhqr_batched.h with T = float; a single matrix is a batch of 1).  The
  *                            matrix is stored in float, every sum (column norm, v_j' a_c) is taken in double -- the product of
  *                            two floats is exact there --, alpha / f / pivot are formed in double, every stored entry is
  *                            rounded to float once per column step; the solve carries b in double and rounds each entry once.
