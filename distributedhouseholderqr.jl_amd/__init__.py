@@ -18,7 +18,8 @@ from .api import (Context, DistributedHouseholderQRStruct, apply_q_, bench_check
                   bench_stream_gbps, empty_colmajor, empty_colmajor_batched, empty_colmajor_batched_c, get_context, get_q, get_r, householder_, ldiv,
                   ldiv_batched, partialdot, qr_, qr_batched_, rand_colmajor, rand_colmajor_batched, rand_colmajor_batched_c, rand_colmajor_c, rand_vector_device, residual, solve_householder_,
                   apply_q_batched_, form_q_batched, form_r_batched, solve_batched_nrhs,
-                  ldiv_pivoted_batched, lstsq_batched, qr_pivoted_batched_, rank_batched)
+                  ldiv_pivoted_batched, lstsq_batched, qr_pivoted_batched_, rank_batched,
+                  factor_pivoted_batched_, lstsq_pivoted_batched, rank_pivoted_batched, solve_pivoted_batched)
 from .distributed import ColumnCyclicQR, Communicator, MultiGpuQR, ldiv_darray_, qr_darray_, qr_darray_c64_, qr_multi_
 from .rowsplit import RowSplitQR
 from .partition import BlockCyclicColumns, LocalColumnBlock, contiguous_column_blocks
@@ -30,4 +31,5 @@ __all__ = [
     "solve_householder_", "empty_colmajor_batched", "rand_colmajor_batched", "empty_colmajor_batched_c", "rand_colmajor_batched_c", "qr_batched_", "ldiv_batched", "ColumnCyclicQR", "Communicator", "MultiGpuQR", "ldiv_darray_", "qr_darray_", "qr_darray_c64_", "qr_multi_", "RowSplitQR", "BlockCyclicColumns", "LocalColumnBlock", "contiguous_column_blocks",
     "solve_batched_nrhs", "apply_q_batched_", "form_q_batched", "form_r_batched",
     "qr_pivoted_batched_", "rank_batched", "ldiv_pivoted_batched", "lstsq_batched",
+    "factor_pivoted_batched_", "rank_pivoted_batched", "solve_pivoted_batched", "lstsq_pivoted_batched",
 ]

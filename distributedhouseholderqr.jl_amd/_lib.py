@@ -114,6 +114,18 @@ SIGNATURES = {
                                               _i64, _i64]),
     "dhqr_qr_batched_pivoted_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
     "dhqr_lstsq_batched_f64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64]),
+    "dhqr_factor_batched_pivoted_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_rank_batched_f32": (_i32, [_p, _p, _i64, _i64, _i64, _f64, _p, _i64]),
+    "dhqr_solve_batched_pivoted_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64,
+                                              _i64, _i64]),
+    "dhqr_qr_batched_pivoted_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_lstsq_batched_f32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64]),
+    "dhqr_factor_batched_pivoted_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_rank_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _f64, _p, _i64]),
+    "dhqr_solve_batched_pivoted_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64,
+                                              _i64, _i64]),
+    "dhqr_qr_batched_pivoted_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64]),
+    "dhqr_lstsq_batched_c64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64]),
     "dhqr_partialdot_f64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_partialdot_host_f64": (_i32, [_p, _p, _p, _i64, _i64, _pd]),
     "dhqr_factor_c64": (_i32, [_p, _p, _i64, _i64, _i64, _p]),

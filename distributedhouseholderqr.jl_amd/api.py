@@ -881,6 +881,181 @@ def lstsq_batched(A, B, rcond=None):
     return (X[:, :, 0] if vec else X), rank
 
 
+# ---- the same four for every element type (float64: the functions above, their bytes; float32 and complex128: dhqr_*_f32 / _c64)
+def _pivoted_sfx(A, what):
+    """"f64", "f32" or "c64" for the element type of a numpy array or tensor; anything else is a TypeError"""
+    if not (_is_tensor(A) or isinstance(A, np.ndarray)):
+        raise TypeError(f"{what}: numpy array or CUDA tensor expected")
+    xp = torch if _is_tensor(A) else np
+    sfx = {xp.float64: "f64", xp.float32: "f32", xp.complex128: "c64"}.get(A.dtype if _is_tensor(A) else A.dtype.type)
+    if sfx is None:
+        raise TypeError(f"{what}: float64, float32 or complex128 expected, got {A.dtype}")
+    return sfx
+
+
+def _pivoted_any(A, what):
+    """(A (batch, m, n), on the device?, suffix) of an argument of the typed pivoted functions (a 2-D A is a batch of one)"""
+    sfx = _pivoted_sfx(A, what)
+    if A.ndim == 2:
+        A = A[None]
+    if A.ndim != 3:
+        raise ValueError(f"{what}: (batch, m, n) or (m, n) array expected")
+    if _is_tensor(A) and not A.is_cuda:
+        raise TypeError(f"{what}: device path needs a CUDA tensor")
+    return A, _is_tensor(A), sfx
+
+
+def _pivoted_rhs(b, A, batch, m, dev, what="B"):
+    """(B (batch, m, nrhs), was it (batch, m)?); a dtype or residence other than the factor's is a TypeError"""
+    if not (_is_tensor(b) or isinstance(b, np.ndarray)) or _is_tensor(b) != dev:
+        raise TypeError(f"{what}: a {'CUDA tensor' if dev else 'numpy array'} like the matrices expected")
+    if b.dtype != A.dtype:
+        raise TypeError(f"{what} is {b.dtype} but the factor is {A.dtype}: convert it explicitly")
+    if dev and not b.is_cuda:
+        raise TypeError(f"{what}: a CUDA tensor like the matrices expected")
+    vec = b.ndim == 2
+    if vec:
+        b = b[:, :, None]
+    if b.ndim != 3 or tuple(b.shape[:2]) != (batch, m):
+        raise ValueError(f"{what} must have shape ({batch}, {m}) or ({batch}, {m}, nrhs)")
+    return b, vec
+
+
+def _empty_colmajor_like(A, batch, m, n, device):
+    return torch.empty((batch, n, m), dtype=A.dtype, device=device).transpose(1, 2)
+
+
+def factor_pivoted_batched_(A) -> DistributedHouseholderQRStruct:
+    """qr_pivoted_batched_ for every element type: qr!(A[k]) with COLUMN PIVOTING for every matrix of a (batch, m, n) float64,
+    float32 or complex128 batch (a 2-D A is a batch of one): dhqr_factor_batched_pivoted_* on a CUDA tensor with column-major
+    matrices, dhqr_qr_batched_pivoted_* on a numpy array.  Mutates A; returns the struct with α (batch, n) and jpvt (batch, n)
+    int32.  form_q_batched, form_r_batched and apply_q_batched_ take the struct unchanged: A[k][:, jpvt[k]] = Q[k] R[k]."""
+    A, dev, sfx = _pivoted_any(A, "A")
+    if sfx == "f64":
+        return qr_pivoted_batched_(A)
+    L = _lib.lib()
+    batch, m, n = A.shape
+    if dev:
+        lay = _batch_layout(A.shape, A.stride())
+        if lay is None:
+            raise ValueError("matrices of the batch must be column-major (stride(1) == 1); build it with empty_colmajor_batched")
+        H = DistributedHouseholderQRStruct(A, jpvt=torch.zeros((batch, n), dtype=torch.int32, device=A.device))
+        ctx = get_context(A.device.index)
+        ctx.use_torch_stream()
+        check(getattr(L, f"dhqr_factor_batched_pivoted_{sfx}")(ctx.handle, _vp(A), m, n, lay[0], lay[1], _vp(H.α), max(n, 1),
+                                                               _vp(H.jpvt), max(n, 1), batch))
+        ctx.synchronize()
+        return H
+    F, lda, strideA = _host_batch(A)
+    H = DistributedHouseholderQRStruct(A, jpvt=np.zeros((batch, n), dtype=np.int32))
+    check(getattr(L, f"dhqr_qr_batched_pivoted_{sfx}")(get_context().handle, _vp(F), m, n, lda, strideA, _vp(H.α), max(n, 1),
+                                                       _vp(H.jpvt), max(n, 1), batch))
+    if F is not A:
+        A[...] = F
+    return H
+
+
+def _pivoted_struct_any(H):
+    """(A (batch, m, n), α, jpvt, on the device?, suffix) of a struct factor_pivoted_batched_ returned"""
+    if getattr(H, "jpvt", None) is None:
+        raise TypeError("a pivoted factorisation (factor_pivoted_batched_) expected: the struct has no jpvt")
+    A, dev, sfx = _pivoted_any(H.A, "H.A")
+    batch, m, n = A.shape
+    if not (_is_tensor(H.α) or isinstance(H.α, np.ndarray)) or H.α.dtype != A.dtype:
+        raise TypeError(f"α is {getattr(H.α, 'dtype', type(H.α))} but the factor is {A.dtype}")
+    xp = torch if dev else np
+    for v, dt, name in ((H.α, A.dtype, "α"), (H.jpvt, xp.int32, "jpvt")):
+        if _is_tensor(v) != dev or v.dtype != dt or tuple(v.shape) != (batch, n) or (dev and not (v.is_cuda and v.is_contiguous())):
+            raise TypeError(f"{name} must be a contiguous {dt} {'CUDA tensor' if dev else 'numpy array'} of shape ({batch}, {n})")
+    if dev:
+        return A, H.α, H.jpvt, True, sfx
+    return A, np.ascontiguousarray(H.α), np.ascontiguousarray(H.jpvt), False, sfx
+
+
+def rank_pivoted_batched(H: DistributedHouseholderQRStruct, rcond=None):
+    """rank_batched for every element type (dhqr_rank_batched_*): the number of leading j with |α_j| > rc |α_0|, rc = rcond, or
+    max(m, n) eps of the element type when rcond is None or negative; (batch,) int32, where the factor is."""
+    A, α, _, dev, sfx = _pivoted_struct_any(H)
+    if sfx == "f64":
+        return rank_batched(H, rcond)
+    L = _lib.lib()
+    batch, m, n = A.shape
+    if batch == 0 or n == 0:
+        return torch.zeros((batch,), dtype=torch.int32, device=A.device) if dev else np.zeros((batch,), dtype=np.int32)
+    ctx = get_context(A.device.index if dev else None)
+    ctx.use_torch_stream()
+    d = α if dev else torch.from_numpy(α).to(f"cuda:{ctx.device}")
+    rank = torch.zeros((batch,), dtype=torch.int32, device=d.device)
+    check(getattr(L, f"dhqr_rank_batched_{sfx}")(ctx.handle, _vp(d), m, n, max(n, 1), _rcond(rcond), _vp(rank), batch))
+    ctx.synchronize()
+    return rank if dev else rank.cpu().numpy()
+
+
+def solve_pivoted_batched(H: DistributedHouseholderQRStruct, B, rcond=None):
+    """ldiv_pivoted_batched for every element type: rank_pivoted_batched(H, rcond), then dhqr_solve_batched_pivoted_* on a copy
+    of B.  B (batch, m) -> X (batch, n); B (batch, m, nrhs) -> X (batch, n, nrhs), column-major matrices.  X[k][jpvt[k][i]] = z_i
+    for i < rank, exact zeros elsewhere; B is not modified.  A B of another dtype than the factor's is a TypeError."""
+    A, α, jpvt, dev, sfx = _pivoted_struct_any(H)
+    batch, m, n = A.shape
+    B, vec = _pivoted_rhs(B, A, batch, m, dev)
+    if sfx == "f64":
+        return ldiv_pivoted_batched(H, B[:, :, 0] if vec else B, rcond)
+    L = _lib.lib()
+    nrhs = B.shape[2]
+    ctx = get_context(A.device.index if dev else None)
+    ctx.use_torch_stream()
+    device = A.device if dev else f"cuda:{ctx.device}"
+    if dev:
+        dA, dal, djp = A, α, jpvt
+    else:  # (the C ABI has no host form of the solve alone: stage with torch)
+        tA = torch.from_numpy(np.ascontiguousarray(A))
+        dA = _empty_colmajor_like(tA, batch, m, n, device)
+        dA.copy_(tA)
+        dal, djp = torch.from_numpy(α).to(device), torch.from_numpy(jpvt).to(device)
+    lay = _batch_layout(dA.shape, dA.stride())
+    if lay is None:
+        raise ValueError("matrices of the batch must be column-major (stride(1) == 1)")
+    rank = torch.zeros((batch,), dtype=torch.int32, device=device)
+    W = _empty_colmajor_like(dA, batch, m, nrhs, device)
+    W.copy_(B if dev else torch.from_numpy(np.ascontiguousarray(B)))
+    X = _empty_colmajor_like(dA, batch, n, nrhs, device)
+    if batch and n and nrhs:
+        check(getattr(L, f"dhqr_rank_batched_{sfx}")(ctx.handle, _vp(dal), m, n, max(n, 1), _rcond(rcond), _vp(rank), batch))
+        check(getattr(L, f"dhqr_solve_batched_pivoted_{sfx}")(ctx.handle, _vp(dA), m, n, lay[0], lay[1], _vp(dal), max(n, 1), _vp(djp),
+                                                              max(n, 1), _vp(rank), _vp(W), nrhs, max(m, 1), max(m * nrhs, 1), _vp(X),
+                                                              max(n, 1), max(n * nrhs, 1), batch))
+    ctx.synchronize()
+    if not dev:
+        X = X.cpu().numpy()
+    return X[:, :, 0] if vec else X
+
+
+def lstsq_pivoted_batched(A, B, rcond=None):
+    """lstsq_batched for every element type: min ||A[k] x - B[k]|| for every matrix of a (batch, m, n) batch, rank-deficient
+    matrices included.  Returns (X, rank); A and B are not modified.  numpy arrays: dhqr_lstsq_batched_*; CUDA tensors: the
+    three device entry points on copies.  A B of another dtype than A's is a TypeError."""
+    A, dev, sfx = _pivoted_any(A, "A")
+    batch, m, n = A.shape
+    B, vec = _pivoted_rhs(B, A, batch, m, dev)
+    if sfx == "f64":
+        return lstsq_batched(A, B[:, :, 0] if vec else B, rcond)
+    L = _lib.lib()
+    nrhs = B.shape[2]
+    if dev:
+        W = _empty_colmajor_like(A, batch, m, n, A.device)
+        W.copy_(A)
+        H = factor_pivoted_batched_(W)
+        X = solve_pivoted_batched(H, B, rcond)
+        return (X[:, :, 0] if vec else X), rank_pivoted_batched(H, rcond)
+    F, lda, strideA = _host_batch(A)
+    Bf, ldb, strideB = _host_batch(B)
+    X = np.zeros((batch, nrhs, n), dtype=A.dtype).transpose(0, 2, 1)
+    rank = np.zeros((batch,), dtype=np.int32)
+    check(getattr(L, f"dhqr_lstsq_batched_{sfx}")(get_context().handle, _vp(F), m, n, lda, strideA, _vp(Bf), nrhs, ldb, strideB,
+                                                  _rcond(rcond), _vp(X), max(n, 1), max(n * nrhs, 1), _vp(rank), batch))
+    return (X[:, :, 0] if vec else X), rank
+
+
 def _partialdot_c64(a, b, lo: int, hi: int) -> complex:
     """partialdot(a, b, lo:hi-1, ComplexF64) (src:51-59): sum conj(a[i]) b[i]"""
     L = _lib.lib()

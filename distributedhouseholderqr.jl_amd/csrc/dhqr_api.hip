@@ -19,6 +19,7 @@
 #include "dhqr_batched_nrhs.h"
 #include "dhqr_batched_applyq.h"
 #include "dhqr_batched_pivoted.h"
+#include "dhqr_batched_complex_pivoted.h"
 #include "dhqr_tsqr.h"
 
 static thread_local char g_err[512] = "";
@@ -2219,8 +2220,9 @@ int32_t dhqr_form_r_batched_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t
   return form_r_batched(c, dA, n, lda, strideA, dalpha, stride_alpha, dR, ldr, strideR, batch);
 }
 
-// Column-pivoted QR, the numerical rank and the rank-truncated solve for batches, Float64 (dhqr.h:
-// dhqr_factor_batched_pivoted_f64 ...); kernels: dhqr_batched_pivoted.h
+// Column-pivoted QR, the numerical rank and the rank-truncated solve for batches, Float64 and Float32 (dhqr.h:
+// dhqr_factor_batched_pivoted_f64 ...; the ComplexF64 forms stand with the other _c64 entry points); kernels:
+// dhqr_batched_pivoted.h, dhqr_batched_complex_pivoted.h; host side: dhqr_batched_host.h
 int32_t dhqr_factor_batched_pivoted_f64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
                                         int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch) {
   ENTER(c);
@@ -2267,6 +2269,57 @@ int32_t dhqr_lstsq_batched_f64(dhqr_ctx *c, const double *hA, int64_t m, int64_t
                                int32_t *hrank, int64_t batch) {
   ENTER(c);
   const double one = 1.0;  // (the checker wants an alpha: the staged factor has its own)
+  CHECK_BATCHED(hA, m, n, lda, strideA, &one, n, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB), rhs_block(hX, nrhs, ldx, strideX));
+  if (!hrank) return set_err(DHQR_EINVAL, "null rank pointer");
+  return lstsq_host(c, hA, m, n, lda, strideA, hB, nrhs, ldb, strideB, rcond, hX, ldx, strideX, hrank, batch);
+}
+
+int32_t dhqr_factor_batched_pivoted_f32(dhqr_ctx *c, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *dalpha,
+                                        int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_pivoted(djpvt, n, stride_jpvt));
+  return factor_batched_pivoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, djpvt, stride_jpvt, batch);
+}
+
+int32_t dhqr_rank_batched_f32(dhqr_ctx *c, const float *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond, int32_t *drank,
+                              int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (m < 0 || n < 0 || m < n) return set_err(DHQR_EINVAL, "m >= n >= 0 required (m=%lld n=%lld)", (long long)m, (long long)n);
+  if (batch == 0 || n == 0) return DHQR_OK;  // (nothing to do, as in the whole batched family)
+  if (!dalpha || !drank) return set_err(DHQR_EINVAL, "null alpha or rank pointer");
+  if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
+  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
+  return rank_batched(c, dalpha, m, n, stride_alpha, rcond, drank, batch);
+}
+
+int32_t dhqr_solve_batched_pivoted_f32(dhqr_ctx *c, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                       const float *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
+                                       const int32_t *drank, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, float *dX,
+                                       int64_t ldx, int64_t strideX, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_block(dB, nrhs, ldb, strideB),
+                rhs_block(dX, nrhs, ldx, strideX));
+  CHECK(check_pivoted(djpvt, n, stride_jpvt));
+  if (!drank) return set_err(DHQR_EINVAL, "null rank pointer");
+  return solve_batched_pivoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, djpvt, stride_jpvt, drank, dB, nrhs, ldb,
+                               strideB, dX, ldx, strideX, batch);
+}
+
+int32_t dhqr_qr_batched_pivoted_f32(dhqr_ctx *c, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
+                                    int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr);
+  CHECK(check_pivoted(hjpvt, n, stride_jpvt));
+  return qr_pivoted_host(c, hA, m, n, lda, strideA, halpha, stride_alpha, hjpvt, stride_jpvt, batch);
+}
+
+int32_t dhqr_lstsq_batched_f32(dhqr_ctx *c, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *hB,
+                               int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, float *hX, int64_t ldx, int64_t strideX,
+                               int32_t *hrank, int64_t batch) {
+  ENTER(c);
+  const float one = 1;  // (the checker wants an alpha: the staged factor has its own)
   CHECK_BATCHED(hA, m, n, lda, strideA, &one, n, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB), rhs_block(hX, nrhs, ldx, strideX));
   if (!hrank) return set_err(DHQR_EINVAL, "null rank pointer");
   return lstsq_host(c, hA, m, n, lda, strideA, hB, nrhs, ldb, strideB, rcond, hX, ldx, strideX, hrank, batch);
@@ -2769,6 +2822,65 @@ int32_t dhqr_form_r_batched_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_
   CHECK(check_zptr(dalpha, "alpha"));
   CHECK(check_zptr(dR, "R"));
   return form_r_batched(c, ZC(dA), n, lda, strideA, ZC(dalpha), stride_alpha, ZM(dR), ldr, strideR, batch);
+}
+// Column-pivoted QR, the numerical rank and the rank-truncated solve for batches, ComplexF64 (kernels:
+// dhqr_batched_complex_pivoted.h)
+int32_t dhqr_factor_batched_pivoted_c64(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
+                                        int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr);
+  CHECK(check_pivoted(djpvt, n, stride_jpvt));
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  return factor_batched_pivoted(c, ZM(dA), m, n, lda, strideA, ZM(dalpha), stride_alpha, djpvt, stride_jpvt, batch);
+}
+
+int32_t dhqr_rank_batched_c64(dhqr_ctx *c, const double *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond, int32_t *drank,
+                              int64_t batch) {
+  ENTER(c);
+  if (batch < 0) return set_err(DHQR_EINVAL, "negative batch %lld", (long long)batch);
+  if (m < 0 || n < 0 || m < n) return set_err(DHQR_EINVAL, "m >= n >= 0 required (m=%lld n=%lld)", (long long)m, (long long)n);
+  if (batch == 0 || n == 0) return DHQR_OK;  // (nothing to do, as in the whole batched family)
+  if (!dalpha || !drank) return set_err(DHQR_EINVAL, "null alpha or rank pointer");
+  if (batch > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch %lld too large", (long long)batch);
+  if (stride_alpha < n) return set_err(DHQR_EINVAL, "stride_alpha %lld < n=%lld", (long long)stride_alpha, (long long)n);
+  CHECK(check_zptr(dalpha, "alpha"));
+  return rank_batched(c, ZC(dalpha), m, n, stride_alpha, rcond, drank, batch);
+}
+
+int32_t dhqr_solve_batched_pivoted_c64(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                       const double *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
+                                       const int32_t *drank, double *dB, int64_t nrhs, int64_t ldb, int64_t strideB, double *dX,
+                                       int64_t ldx, int64_t strideX, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(dA, m, n, lda, strideA, dalpha, stride_alpha, batch, nullptr, rhs_block(dB, nrhs, ldb, strideB),
+                rhs_block(dX, nrhs, ldx, strideX));
+  CHECK(check_pivoted(djpvt, n, stride_jpvt));
+  if (!drank) return set_err(DHQR_EINVAL, "null rank pointer");
+  CHECK(check_zptr(dA, "matrix"));
+  CHECK(check_zptr(dalpha, "alpha"));
+  CHECK(check_zptr(dB, "B"));
+  CHECK(check_zptr(dX, "X"));
+  return solve_batched_pivoted(c, ZC(dA), m, n, lda, strideA, ZC(dalpha), stride_alpha, djpvt, stride_jpvt, drank, ZM(dB), nrhs, ldb,
+                               strideB, ZM(dX), ldx, strideX, batch);
+}
+
+int32_t dhqr_qr_batched_pivoted_c64(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
+                                    int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch) {
+  ENTER(c);
+  CHECK_BATCHED(hA, m, n, lda, strideA, halpha, stride_alpha, batch, nullptr);
+  CHECK(check_pivoted(hjpvt, n, stride_jpvt));
+  return qr_pivoted_host(c, ZM(hA), m, n, lda, strideA, ZM(halpha), stride_alpha, hjpvt, stride_jpvt, batch);
+}
+
+int32_t dhqr_lstsq_batched_c64(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *hB,
+                               int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, double *hX, int64_t ldx, int64_t strideX,
+                               int32_t *hrank, int64_t batch) {
+  ENTER(c);
+  const double one[2] = {1.0, 0.0};  // (the checker wants an alpha: the staged factor has its own)
+  CHECK_BATCHED(hA, m, n, lda, strideA, one, n, batch, nullptr, rhs_block(hB, nrhs, ldb, strideB), rhs_block(hX, nrhs, ldx, strideX));
+  if (!hrank) return set_err(DHQR_EINVAL, "null rank pointer");
+  return lstsq_host(c, ZC(hA), m, n, lda, strideA, ZC(hB), nrhs, ldb, strideB, rcond, ZM(hX), ldx, strideX, hrank, batch);
 }
 #undef ZC
 #undef ZM

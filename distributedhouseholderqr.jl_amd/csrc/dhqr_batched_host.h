@@ -651,50 +651,100 @@ static int32_t ldiv_host(dhqr_ctx *c, const T *hA, int64_t m, int64_t n, int64_t
   return host_finish(c, rc, false);
 }
 
-// ---- column-pivoted QR, the rank, the rank-truncated solve (dhqr.h: dhqr_factor_batched_pivoted_f64 ...; Float64 only) -----
-// Wave tier: ONE launch of the kernels of dhqr_batched_pivoted.h; every other shape, and every shape with the small route
-// off: ONE launch of their general forms, a workgroup per matrix / per (matrix, column of B).
+// ---- column-pivoted QR, the rank, the rank-truncated solve (dhqr.h: dhqr_factor_batched_pivoted_f64 ...), written once for
+// T = double, float and double2 (ComplexF64; lda and the strides count complex elements) -------------------------------------
+// Float64, ComplexF64.  Wave tier: ONE launch of the kernels of dhqr_batched_pivoted.h / dhqr_batched_complex_pivoted.h; every
+// other shape, and every shape with the small route off: ONE launch of their general forms, a workgroup per matrix / per
+// (matrix, column of B).  Float32: the wave tier natively (the same kernels with T = float); everything else PROMOTED --
+// widened into the Float64 workspace, the Float64 route (its jpvt, written straight into the caller's), rounded back.
 static int32_t check_pivoted(const void *jpvt, int64_t n, int64_t stride_jpvt) {
   if (!jpvt) return set_err(DHQR_EINVAL, "null jpvt pointer");
   if (stride_jpvt < n) return set_err(DHQR_EINVAL, "stride_jpvt %lld < n=%lld", (long long)stride_jpvt, (long long)n);
   return DHQR_OK;
 }
-static int32_t factor_batched_pivoted(dhqr_ctx *c, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *dalpha,
+template <typename T>
+static int32_t factor_batched_pivoted(dhqr_ctx *c, T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *dalpha,
                                       int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch) {
-  c->tc_valid = false;  // whatever was kept for one of these matrices is gone
-  c->retry.valid = false;
+  const bool wave = batched_wave_fit(c, m, n);
+  if constexpr (std::is_same_v<T, float>) {
+    if (!wave)
+      return f32_promoted(c, dA, m, n, lda, strideA, dalpha, stride_alpha, nullptr, 0, 0, 0, batch, false, [&](const F32Ws &w) {
+        return factor_batched_pivoted(c, w.A, m, n, m, m * n, w.alpha, n, djpvt, stride_jpvt, batch);
+      });
+  }
+  if constexpr (std::is_same_v<T, double>) {
+    c->tc_valid = false;  // whatever was kept for one of these matrices is gone
+    c->retry.valid = false;
+  }
   CHECK(prof_begin(c, CAT_RANK1));  // ONE launch, one group
-  if (batched_wave_fit(c, m, n)) {
-    WAVE_LAUNCH(k_batched_qrp_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt, stride_jpvt, batch);
-  } else {
+  if (wave) {
+    if constexpr (std::is_same_v<T, double2>)
+      WAVE_LAUNCH(k_batched_zqrp_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt, stride_jpvt, batch);
+    else
+      WAVE_LAUNCH_T(k_batched_qrp_wave, WAVE_TARGS(T), n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt,
+                    stride_jpvt, batch);
+  } else if constexpr (std::is_same_v<T, double2>) {
+    hipLaunchKernelGGL(k_batched_zqrp_general, dim3((unsigned)batch), dim3(BQPG_THREADS), 0, c->stream, dA, lda, strideA, m, n, dalpha,
+                       stride_alpha, djpvt, stride_jpvt);
+    LAUNCHCHECK();
+  } else if constexpr (std::is_same_v<T, double>) {
     hipLaunchKernelGGL(k_batched_qrp_general, dim3((unsigned)batch), dim3(BQPG_THREADS), 0, c->stream, dA, lda, strideA, m, n, dalpha,
                        stride_alpha, djpvt, stride_jpvt);
     LAUNCHCHECK();
   }
   if (c->profiling)  // (the update's traffic, as the unpivoted factor counts it; the pivot search reads as much again)
-    for (int64_t j = 0; j + 1 < n; ++j) c->st.bytes_rank1 += (double)batch * 16.0 * (double)(m - j) * (double)(n - j - 1);
+    for (int64_t j = 0; j + 1 < n; ++j)
+      c->st.bytes_rank1 += (double)batch * (double)(2 * sizeof(T)) * (double)(m - j) * (double)(n - j - 1);
   return prof_end(c);
 }
-// one element-wise launch, not counted
-static int32_t rank_batched(dhqr_ctx *c, const double *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond, int32_t *drank,
+// one element-wise launch, not counted.  rcond < 0: max(m, n) eps(T) -- 2^-52 for Float64 and ComplexF64, 2^-23 for Float32
+template <typename T>
+static int32_t rank_batched(dhqr_ctx *c, const T *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond, int32_t *drank,
                             int64_t batch) {
-  const double rc = rcond >= 0.0 ? rcond : (double)std::max(m, n) * 0x1p-52;
-  hipLaunchKernelGGL(k_batched_rank, dim3((unsigned)std::min<int64_t>((batch + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dalpha, n,
-                     stride_alpha, rc, drank, batch);
+  const double rc = rcond >= 0.0 ? rcond : (double)std::max(m, n) * (std::is_same_v<T, float> ? 0x1p-23 : 0x1p-52);
+  hipLaunchKernelGGL(k_batched_rank<T>, dim3((unsigned)std::min<int64_t>((batch + 255) / 256, 256 * 32)), dim3(256), 0, c->stream, dalpha,
+                     n, stride_alpha, rc, drank, batch);
   LAUNCHCHECK();
   return DHQR_OK;
 }
-static int32_t solve_batched_pivoted(dhqr_ctx *c, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
-                                     const double *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
-                                     const int32_t *drank, double *dB, int64_t nrhs, int64_t ldb, int64_t strideB, double *dX, int64_t ldx,
-                                     int64_t strideX, int64_t batch) {
+template <typename T>
+static int32_t solve_batched_pivoted(dhqr_ctx *c, const T *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *dalpha,
+                                     int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt, const int32_t *drank, T *dB,
+                                     int64_t nrhs, int64_t ldb, int64_t strideB, T *dX, int64_t ldx, int64_t strideX, int64_t batch) {
   const bool wave = batched_wave_fit(c, m, n);
   if (!wave && batch * nrhs > 0x7fffffffLL) return set_err(DHQR_EINVAL, "batch * nrhs = %lld too large", (long long)(batch * nrhs));
+  if constexpr (std::is_same_v<T, float>) {
+    if (!wave) {
+      // PROMOTED.  The workspace: matrices | alphas | B | X, packed, each section on an even element.  X is widened too: the
+      // entries the Float64 route does not write (a jpvt entry out of range) keep the caller's values through the rounding.
+      const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
+      const size_t nB = (size_t)m * (size_t)nrhs * (size_t)batch, nX = (size_t)n * (size_t)nrhs * (size_t)batch;
+      CHECK(ensure(c, c->f32_ws, f32_even(na) + f32_even(nal) + f32_even(nB) + nX));
+      double *wA = c->f32_ws.p, *wal = wA + f32_even(na), *wB = wal + f32_even(nal), *wX = wB + f32_even(nB);
+      if (c->tc_A == wA) c->tc_valid = false;  // the caller's factor is widened afresh: nothing kept applies to it
+      CHECK(f32_convert_launch(c, true, dA, lda, strideA, wA, m, m * n, m, n, batch));
+      CHECK(f32_convert_launch(c, true, dalpha, n, stride_alpha, wal, n, n, n, 1, batch));
+      CHECK(f32_convert_launch(c, true, dB, ldb, strideB, wB, m, m * nrhs, m, nrhs, batch));
+      CHECK(f32_convert_launch(c, true, dX, ldx, strideX, wX, n, n * nrhs, n, nrhs, batch));
+      CHECK(solve_batched_pivoted(c, (const double *)wA, m, n, m, m * n, (const double *)wal, n, djpvt, stride_jpvt, drank, wB, nrhs, m,
+                                  m * nrhs, wX, n, n * nrhs, batch));
+      CHECK(f32_convert_launch(c, false, wB, m, m * nrhs, dB, ldb, strideB, m, nrhs, batch));
+      return f32_convert_launch(c, false, wX, n, n * nrhs, dX, ldx, strideX, n, nrhs, batch);
+    }
+  }
   CHECK(prof_begin(c, CAT_SOLVE));  // ONE launch, one group, whatever nrhs and batch
   if (wave) {
-    WAVE_LAUNCH(k_batched_ldivp_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt, stride_jpvt, drank, dB,
-                (int)nrhs, ldb, strideB, dX, ldx, strideX, batch);
-  } else {
+    if constexpr (std::is_same_v<T, double2>)
+      WAVE_LAUNCH(k_batched_zldivp_wave, n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt, stride_jpvt, drank, dB,
+                  (int)nrhs, ldb, strideB, dX, ldx, strideX, batch);
+    else
+      WAVE_LAUNCH_T(k_batched_ldivp_wave, WAVE_TARGS(T), n, batch, dA, lda, strideA, (int)m, (int)n, dalpha, stride_alpha, djpvt,
+                    stride_jpvt, drank, dB, (int)nrhs, ldb, strideB, dX, ldx, strideX, batch);
+  } else if constexpr (std::is_same_v<T, double2>) {
+    hipLaunchKernelGGL(k_batched_zldivp_general, dim3((unsigned)(batch * nrhs)), dim3(BQPG_THREADS), 0, c->stream, dA, lda, strideA, m, n,
+                       dalpha, stride_alpha, djpvt, stride_jpvt, drank, dB, nrhs, ldb, strideB, dX, ldx, strideX);
+    LAUNCHCHECK();
+  } else if constexpr (std::is_same_v<T, double>) {
     hipLaunchKernelGGL(k_batched_ldivp_general, dim3((unsigned)(batch * nrhs)), dim3(BQPG_THREADS), 0, c->stream, dA, lda, strideA, m, n,
                        dalpha, stride_alpha, djpvt, stride_jpvt, drank, dB, nrhs, ldb, strideB, dX, ldx, strideX);
     LAUNCHCHECK();
@@ -702,19 +752,24 @@ static int32_t solve_batched_pivoted(dhqr_ctx *c, const double *dA, int64_t m, i
   return prof_end(c);
 }
 
-// The host forms.  The staging area (the buffer of dhqr_qr_batched_f64; dhqr_trim releases it), in doubles: matrices | alphas
-// | B | X | then the int32 sections jpvt and rank (each padded to a whole double).
+// The host forms.  The staging area (the buffer of dhqr_qr_batched_f64 / _f32; dhqr_trim releases it), in elements of T:
+// matrices | alphas | B | X | then the int32 sections jpvt and rank (each padded to a whole element).
 static int32_t batch_copy_i32(dhqr_ctx *c, int32_t *d, int32_t *h, int64_t count, int64_t hstride, int64_t batch) {
   HIPCHECK(hipMemcpy2DAsync(h, hstride * sizeof(int32_t), d, count * sizeof(int32_t), count * sizeof(int32_t), batch, hipMemcpyDeviceToHost,
                             c->stream));
   return DHQR_OK;
 }
-static int32_t qr_pivoted_host(dhqr_ctx *c, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
-                               int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch) {
+template <typename T>
+static inline size_t i32_elems(size_t count) {  // elements of T that hold `count` int32
+  return (count * sizeof(int32_t) + sizeof(T) - 1) / sizeof(T);
+}
+template <typename T>
+static int32_t qr_pivoted_host(dhqr_ctx *c, T *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, T *halpha, int64_t stride_alpha,
+                               int32_t *hjpvt, int64_t stride_jpvt, int64_t batch) {
   const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
-  double *dA;
-  CHECK(staging(c, na + nal + (nal + 1) / 2, dA));
-  double *dal = dA + na;
+  T *dA;
+  CHECK(staging(c, na + nal + i32_elems<T>(nal), dA));
+  T *dal = dA + na;
   int32_t *djp = reinterpret_cast<int32_t *>(dal + nal);
   int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
   if (rc == DHQR_OK) rc = factor_batched_pivoted(c, dA, m, n, m, m * n, dal, n, djp, n, batch);
@@ -724,21 +779,23 @@ static int32_t qr_pivoted_host(dhqr_ctx *c, double *hA, int64_t m, int64_t n, in
   return host_finish(c, rc, false);
 }
 // factor a staged copy, the ranks, the solve; X and the ranks out.  hA and hB are read only.
-static int32_t lstsq_host(dhqr_ctx *c, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *hB, int64_t nrhs,
-                          int64_t ldb, int64_t strideB, double rcond, double *hX, int64_t ldx, int64_t strideX, int32_t *hrank,
-                          int64_t batch) {
+template <typename T>
+static int32_t lstsq_host(dhqr_ctx *c, const T *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const T *hB, int64_t nrhs,
+                          int64_t ldb, int64_t strideB, double rcond, T *hX, int64_t ldx, int64_t strideX, int32_t *hrank, int64_t batch) {
   const size_t na = (size_t)m * (size_t)n * (size_t)batch, nal = (size_t)n * (size_t)batch;
   const size_t nB = (size_t)m * (size_t)nrhs * (size_t)batch, nX = (size_t)n * (size_t)nrhs * (size_t)batch;
-  double *dA;
-  CHECK(staging(c, na + nal + nB + nX + (nal + 1) / 2 + ((size_t)batch + 1) / 2, dA));
-  double *dal = dA + na, *dB = dal + nal, *dX = dB + nB;
+  T *dA;
+  CHECK(staging(c, na + nal + nB + nX + i32_elems<T>(nal) + i32_elems<T>((size_t)batch), dA));
+  T *dal = dA + na, *dB = dal + nal, *dX = dB + nB;
   int32_t *djp = reinterpret_cast<int32_t *>(dX + nX);
-  int32_t *drk = reinterpret_cast<int32_t *>(dX + nX + (nal + 1) / 2);
+  int32_t *drk = reinterpret_cast<int32_t *>(dX + nX + i32_elems<T>(nal));
   int32_t rc = batch_copy(c, dA, hA, m, n, lda, strideA, batch, true);
   if (rc == DHQR_OK) rc = batch_copy(c, dB, hB, m, nrhs, ldb, strideB, batch, true);
   if (rc == DHQR_OK) rc = factor_batched_pivoted(c, dA, m, n, m, m * n, dal, n, djp, n, batch);
-  if (rc == DHQR_OK) rc = rank_batched(c, dal, m, n, n, rcond, drk, batch);
-  if (rc == DHQR_OK) rc = solve_batched_pivoted(c, dA, m, n, m, m * n, dal, n, djp, n, drk, dB, nrhs, m, m * nrhs, dX, n, n * nrhs, batch);
+  if (rc == DHQR_OK) rc = rank_batched(c, (const T *)dal, m, n, n, rcond, drk, batch);
+  if (rc == DHQR_OK)
+    rc = solve_batched_pivoted(c, (const T *)dA, m, n, m, m * n, (const T *)dal, n, (const int32_t *)djp, n, (const int32_t *)drk, dB, nrhs,
+                               m, m * nrhs, dX, n, n * nrhs, batch);
   if (rc == DHQR_OK) rc = batch_copy(c, dX, n, n * nrhs, hX, ldx, strideX, n, nrhs, batch, false);
   if (rc == DHQR_OK) rc = batch_copy_i32(c, drk, hrank, 1, 1, batch);
   return host_finish(c, rc, false);

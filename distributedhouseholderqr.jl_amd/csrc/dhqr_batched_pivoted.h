@@ -1,6 +1,6 @@
 // dhqr_batched_pivoted.h -- qr!(A_k) with COLUMN PIVOTING, the numerical rank and the rank-truncated least-squares solve
-// for a batch of small Float64 matrices (dhqr.h: dhqr_factor_batched_pivoted_f64, dhqr_rank_batched_f64,
-// dhqr_solve_batched_pivoted_f64): A_k P_k = Q_k R_k as LAPACK's geqp3 orders it, min ||A_k x - b|| with the columns behind
+// for a batch of small Float64 or Float32 matrices (dhqr.h: dhqr_factor_batched_pivoted_f64 / _f32, dhqr_rank_batched_*,
+// dhqr_solve_batched_pivoted_*; the ComplexF64 kernels: dhqr_batched_complex_pivoted.h): A_k P_k = Q_k R_k as LAPACK's geqp3 orders it, min ||A_k x - b|| with the columns behind
 // the rank dropped as gelsy's basic solution drops them.  The reference has no counterpart; the factor keeps its format
 // (reflectors below the diagonal, R above, alpha on it) and adds one int32 permutation per matrix, so every routine that
 // takes a factor (apply-Q, explicit Q and R) takes a pivoted one unchanged.
@@ -14,6 +14,11 @@
 // there are no more swaps.  The reflector of the chosen column is formed by the expressions of k_batched_qr_wave, except
 // that alphafactor(0) = -1 (as the ComplexF64 routes take it, src:9): a pivot entry that is exactly zero must give a valid
 // reflector here, not alpha = 0.
+//
+// Float32 (T = float, the wave tier alone; every other shape is promoted on the host side): the matrix stored in float, the
+// pivot norms from the stored values widened -- a product of two floats is exact in double --, every sum in double, every
+// stored entry rounded once, as dhqr_wave.h has it for the unpivoted kernels; the zero tail's sqrt(2) is rounded to float.
+// The double instantiations are the kernels as they were before T: the same instructions.
 //
 // Wave tier (m <= 64, n <= 32): k_batched_qr_wave / k_batched_ldiv_wave (dhqr_batched.h) with the pivot step / with the
 // wave's own rank in place of n.  One wave per matrix, BQW_WAVES matrices per workgroup, no LDS, no barrier, no flag, no
@@ -33,39 +38,51 @@
 __device__ __forceinline__ double dhqr_alphafactor_p(double x) { return x > 0.0 ? -1.0 : (x < 0.0 ? 1.0 : (x == 0.0 ? -1.0 : x)); }
 
 #define BQP_SQRT2 1.4142135623730951
+// an empty statement that claims to modify a scalar register: what is derived from it is formed where it is used
+// (BQN_KEEP_IN_LOOP's scalar twin, dhqr_wave.h)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BQP_KEEP_SCALAR(x_) asm volatile("" : "+s"(x_))
+#else
+#define BQP_KEEP_SCALAR(x_) ((void)0)
+#endif
 
 // householder!(A_k P_k, alpha_k) for k < batch, in place; jpvt_k = jpvt + k stride_jpvt receives the n 0-based original
 // indices of the columns.  m <= 64, n <= NC, m >= n >= 1.
-template <int NC>
-__global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_qrp_wave(double *__restrict__ A, int64_t lda, int64_t strideA, int m,
-                                                                     int n, double *__restrict__ alpha, int64_t stride_alpha,
-                                                                     int32_t *__restrict__ jpvt, int64_t stride_jpvt, int64_t batch) {
+template <int NC, typename T>
+__global__ __launch_bounds__(64 * BQW_WAVES, bqw_min_waves<T>(NC)) void k_batched_qrp_wave(T *__restrict__ A, int64_t lda, int64_t strideA, int m,
+                                                                                          int n, T *__restrict__ alpha, int64_t stride_alpha,
+                                                                                          int32_t *__restrict__ jpvt, int64_t stride_jpvt,
+                                                                                          int64_t batch) {
   const int l = bqw_lane();
   const int64_t k = bqw_matrix();
   if (k >= batch) return;  // (the whole wave)
-  double *Ak = A + k * strideA;
-  double a[NC];
+  T *Ak = A + k * strideA;
+  T a[NC];
   bqw_load(a, Ak, lda, m, n, l);
-  double alv = 0.0;  // lane j keeps alpha_j
+  T alv = (T)0;  // lane j keeps alpha_j
   int jp = l;        // lane c keeps jpvt[c]
   int jz = n;        // the first column of the zero tail
 #pragma unroll 1
   for (int j = 0; j < n; ++j) {
     // pivot search: the squared norms of rows >= j of the columns j .. n-1, afresh; the first maximum
+    // (Float32: n as a value of this step's own -- the NC tests c < n of the load would otherwise be carried through the loop
+    // as scalar register pairs and spilled; the Float64 instantiations keep the code they had)
+    int nj = n;
+    if constexpr (!std::is_same_v<T, double>) BQP_KEEP_SCALAR(nj);
     double bestv = -1.0;
     int p = j;
 #pragma unroll
     for (int g = 0; g < NC / 4; ++g) {
-      if (4 * g + 3 >= j && 4 * g < n) {
+      if (4 * g + 3 >= j && 4 * g < nj) {
         double d[4];
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
-          const double t = l >= j ? a[4 * g + cc] : 0.0;
+          const double t = l >= j ? (double)a[4 * g + cc] : 0.0;  // (Float32: the stored value widened, its square exact)
           d[cc] = wave_sum_dpp(t * t);
         }
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
-          const bool take = 4 * g + cc >= j && 4 * g + cc < n && d[cc] > bestv;  // (wave-uniform)
+          const bool take = 4 * g + cc >= j && 4 * g + cc < nj && d[cc] > bestv;  // (wave-uniform)
           bestv = take ? d[cc] : bestv;
           p = take ? 4 * g + cc : p;
         }
@@ -77,31 +94,33 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_q
     }
     // the chosen column, and the one that makes room for it: select chains inside the columns' own groups of four (a chain
     // over all NC columns keeps NC scalar masks alive)
-    double x = 0.0, xj = 0.0;
+    T xt = (T)0, xj = (T)0;
 #pragma unroll
     for (int g = 0; g < NC / 4; ++g) {
       if (g == (p >> 2)) {
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) x = (cc == (p & 3)) ? a[4 * g + cc] : x;
+        for (int cc = 0; cc < 4; ++cc) xt = (cc == (p & 3)) ? a[4 * g + cc] : xt;
       }
       if (g == (j >> 2)) {
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) xj = (cc == (j & 3)) ? a[4 * g + cc] : xj;
       }
     }
+    const double x = (double)xt;
     {
       const int pj = __builtin_amdgcn_readlane(jp, j), pp = __builtin_amdgcn_readlane(jp, p);
       jp = l == j ? pp : (l == p ? pj : jp);
     }
     // reflector j (src:129-140): rows >= m hold zeros
-    const double s2 = bqw_norm2<double>(l >= j ? x : 0.0);
+    const double s2 = bqw_norm2<T>(l >= j ? x : 0.0);
     const double h = smq_readlane(x, j);
     double sn, f, al;
     dhqr_reflector_scalars(s2, h, dhqr_alphafactor_p, sn, f, al);
     const double piv = (h - al) * f;  // src:132
-    const double v = l > j ? x * f : (l == j ? piv : 0.0);  // src:133-140
-    if (l == j) alv = al;
-    const double xv = l >= j ? v : x;  // rows < j keep R
+    const T vt = (T)(l > j ? x * f : (l == j ? piv : 0.0));  // src:133-140 (Float32: rounded once, as k_batched_qr_wave rounds
+    const double v = (double)vt;                              // it; the trailing update uses the stored reflector)
+    if (l == j) alv = (T)al;
+    const T xv = l >= j ? vt : xt;  // rows < j keep R
 #pragma unroll
     for (int g = 0; g < NC / 4; ++g) {  // the swap, then the reflector in its place (p == j: the reflector alone)
       if (g == (p >> 2)) {
@@ -113,12 +132,14 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_q
         for (int cc = 0; cc < 4; ++cc) a[4 * g + cc] = (cc == (j & 3)) ? xv : a[4 * g + cc];
       }
     }
-    bqw_trailing_update(a, v, j, n, l);
+    bqw_trailing_update(a, v, j, nj, l);
   }
   // the zero tail: alpha_c = 0 (alv is 0 in the lanes >= jz), v_c = sqrt(2) e_c for c >= jz
+  int ns = n;
+  if constexpr (!std::is_same_v<T, double>) BQP_KEEP_SCALAR(ns);
 #pragma unroll
-  for (int c = 0; c < NC; ++c) a[c] = (c >= jz && c < n && l >= c) ? (l == c ? BQP_SQRT2 : 0.0) : a[c];
-  bqw_store(a, Ak, lda, m, n, l);
+  for (int c = 0; c < NC; ++c) a[c] = (c >= jz && c < ns && l >= c) ? (l == c ? (T)BQP_SQRT2 : (T)0) : a[c];
+  bqw_store(a, Ak, lda, m, ns, l);
   if (l < n) {
     alpha[k * stride_alpha + l] = alv;
     jpvt[k * stride_jpvt + l] = jp;
@@ -129,19 +150,19 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_q
 // b <- [z; tail] as solve_householder! (k_batched_ldiv_wave's arithmetic) leaves it on the first r columns of the factor,
 // and column q of X_k (n) <- the basic solution x[jpvt[i]] = z_i (i < r), exact zeros elsewhere.  r = 0: b stays untouched.
 // A column's bits do not depend on nrhs, its place or the batch: the columns are taken one after the other.
-template <int NC>
-__global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_ldivp_wave(
-    const double *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, const double *__restrict__ alpha, int64_t stride_alpha,
-    const int32_t *__restrict__ jpvt, int64_t stride_jpvt, const int32_t *__restrict__ rank, double *__restrict__ B, int nrhs, int64_t ldb,
-    int64_t strideB, double *__restrict__ X, int64_t ldx, int64_t strideX, int64_t batch) {
+template <int NC, typename T>
+__global__ __launch_bounds__(64 * BQW_WAVES, bqw_min_waves<T>(NC)) void k_batched_ldivp_wave(
+    const T *__restrict__ A, int64_t lda, int64_t strideA, int m, int n, const T *__restrict__ alpha, int64_t stride_alpha,
+    const int32_t *__restrict__ jpvt, int64_t stride_jpvt, const int32_t *__restrict__ rank, T *__restrict__ B, int nrhs, int64_t ldb,
+    int64_t strideB, T *__restrict__ X, int64_t ldx, int64_t strideX, int64_t batch) {
   int l = bqw_lane();
   const int64_t k = bqw_matrix();
   if (k >= batch) return;  // (the whole wave)
-  double a[NC];
+  T a[NC];
   bqw_load(a, A + k * strideA, lda, m, n, l);
   const int rk = __builtin_amdgcn_readfirstlane(rank[k]);
-  const int r = rk < 0 ? 0 : (rk > n ? n : rk);  // wave-uniform
-  double al = l < r ? alpha[k * stride_alpha + l] : 1.0;  // lane j: alpha_j
+  int r = rk < 0 ? 0 : (rk > n ? n : rk);  // wave-uniform
+  double al = l < r ? (double)alpha[k * stride_alpha + l] : 1.0;  // lane j: alpha_j
   const int jp = l < n ? jpvt[k * stride_jpvt + l] : -1;
   double rinv = dhqr_rcp(al);
 #pragma unroll 1
@@ -150,9 +171,10 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_l
     BQN_KEEP_IN_LOOP(al);
     BQN_KEEP_IN_LOOP(rinv);
     BQN_KEEP_IN_LOOP(l);
-    double *bk = B + k * strideB + (int64_t)q * ldb;
-    dhqr_dd bb[1];
-    bqw_col_set(bb[0], l < m ? bk[l] : 0.0);
+    if constexpr (!std::is_same_v<T, double>) BQP_KEEP_SCALAR(r);  // (Float32: the NC tests c < r formed where they are used)
+    T *bk = B + k * strideB + (int64_t)q * ldb;
+    bqw_col<T> bb[1];
+    bqw_col_set(bb[0], l < m ? (double)bk[l] : 0.0);
     // ---- b <- Q_r'b: reflectors left to right (src:215-224)
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -163,21 +185,26 @@ __global__ __launch_bounds__(64 * BQW_WAVES, BQW_MIN_WAVES(NC)) void k_batched_l
     for (int c = NC - 1; c >= 0; --c)
       if (c < r) bqw_backsub_group(c, l, a[c], al, rinv, bb);
     const double z = bqw_col_value(bb[0]);
-    if (r > 0 && l < m) bk[l] = z;
+    if (r > 0 && l < m) bk[l] = (T)z;  // (Float32: rounded once)
     // jpvt is a permutation: every entry of the column is written once (an index out of range is not written at all)
-    if (l < n && jp >= 0 && jp < n) X[k * strideX + (int64_t)q * ldx + jp] = l < r ? z : 0.0;
+    if (l < n && jp >= 0 && jp < n) X[k * strideX + (int64_t)q * ldx + jp] = l < r ? (T)z : (T)0;
   }
 }
 
 // rank[k] = the number of leading j with |alpha_j| > rc |alpha_0| (counting stops at the first failure; a NaN fails):
-// element-wise, one thread per matrix
-__global__ __launch_bounds__(256) void k_batched_rank(const double *__restrict__ alpha, int64_t n, int64_t stride_alpha, double rc,
+// element-wise, one thread per matrix.  T: the type of an alpha -- double, float (widened: the comparison is in double) or
+// double2 (ComplexF64: |alpha| = hypot(re, im))
+__device__ __forceinline__ double bqp_abs(double x) { return fabs(x); }
+__device__ __forceinline__ double bqp_abs(float x) { return fabs((double)x); }
+__device__ __forceinline__ double bqp_abs(double2 x) { return hypot(x.x, x.y); }
+template <typename T>
+__global__ __launch_bounds__(256) void k_batched_rank(const T *__restrict__ alpha, int64_t n, int64_t stride_alpha, double rc,
                                                       int32_t *__restrict__ rank, int64_t batch) {
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < batch; k += (int64_t)gridDim.x * blockDim.x) {
-    const double *al = alpha + k * stride_alpha;
-    const double bound = rc * fabs(al[0]);
+    const T *al = alpha + k * stride_alpha;
+    const double bound = rc * bqp_abs(al[0]);
     int64_t r = 0;
-    while (r < n && fabs(al[r]) > bound) ++r;
+    while (r < n && bqp_abs(al[r]) > bound) ++r;
     rank[k] = (int32_t)r;
   }
 }

@@ -42,7 +42,9 @@ extern "C" {
                           * dhqr_factor_batched_c64, dhqr_solve_batched_c64, dhqr_qr_batched_c64, dhqr_ldiv_batched_c64;
                           * the one-workgroup ComplexF64 route up to 128 rows behind the existing dhqr_*_c64 names (no new symbol);
                           * dhqr_factor_batched_pivoted_f64, dhqr_rank_batched_f64, dhqr_solve_batched_pivoted_f64,
-                          * dhqr_qr_batched_pivoted_f64, dhqr_lstsq_batched_f64 */
+                          * dhqr_qr_batched_pivoted_f64, dhqr_lstsq_batched_f64;
+                          * the same five for Float32 and ComplexF64: dhqr_factor_batched_pivoted_f32 / _c64, dhqr_rank_batched_f32 / _c64,
+                          * dhqr_solve_batched_pivoted_f32 / _c64, dhqr_qr_batched_pivoted_f32 / _c64, dhqr_lstsq_batched_f32 / _c64 */
 
 #define DHQR_OK 0
 #define DHQR_EINVAL (-1)   /* bad argument (null pointer, m < n, ld < m, unsupported nb ...) */
@@ -448,6 +450,62 @@ int32_t dhqr_solve_batched_pivoted_f64(dhqr_ctx *ctx, const double *dA, int64_t 
 int32_t dhqr_qr_batched_pivoted_f64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
                                     int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch);
 int32_t dhqr_lstsq_batched_f64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *hB,
+                               int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, double *hX, int64_t ldx, int64_t strideX,
+                               int32_t *hrank, int64_t batch);
+
+/* The same five for Float32 and ComplexF64 -- the argument lists of the _f64 forms with the element type changed; ComplexF64
+ * is passed as every _c64 entry point passes it: `double *`, interleaved (re, im), lda and the strides of A, alpha, B and X
+ * counted in COMPLEX elements, device pointers 16-byte aligned.  jpvt and rank stay int32.  Argument rules, the empty calls,
+ * DHQR_EINVAL (nothing is written) and the profiling counts are those of the _f64 forms.  The rule above, per type:
+ *   pivot search   the squared 2-norms of rows >= j of the trailing columns, afresh, in plain double, unscaled: Float32 from
+ *                  the stored float values widened (products and sums in double), ComplexF64 as re^2 + im^2; the smallest
+ *                  column index that attains the maximum, compared with `>`; whole columns and their jpvt entries swap.
+ *   zero tail      a maximum of exactly 0: alpha_c = 0 and v_c = sqrt(2) e_c (real, also for ComplexF64; Float32: sqrt(2)
+ *                  rounded to float) for every remaining column, no more swaps.
+ *   reflector      Float32: the expressions of dhqr_factor_batched_f32's wave kernel (float storage, double sums, every
+ *                  stored entry rounded once), a pivot entry of exactly 0 taking alpha = -norm.  ComplexF64: exactly the
+ *                  expressions of dhqr_factor_batched_c64's wave kernel, whose alphafactor already gives -1 at 0.
+ *   rank           the number of leading j with |alpha_j| > rc |alpha_0|, compared in double; ComplexF64: |alpha| =
+ *                  hypot(re, im); rcond < 0: rc = max(m, n) eps -- 2^-52 for ComplexF64, 2^-23 for Float32.
+ *   solve          r = clamp(drank[k], 0, n); dB_k <- [z; tail] as the type's own unpivoted solve leaves it on the first r
+ *                  columns; dX_k[jpvt[i]] = z_i for i < r, exact zeros (+0, +0 + 0i) elsewhere; r = 0 leaves dB_k untouched;
+ *                  an out-of-range jpvt entry is not written.
+ * Routes:
+ *   m <= 64 and n <= 32      (small route on) ONE launch per call, one WAVE per matrix.  Float32: the kernels of
+ *                            csrc/dhqr_batched_pivoted.h with T = float.  ComplexF64: csrc/dhqr_batched_complex_pivoted.h.  The
+ *                            pivoted factor of A has the BITS of dhqr_factor_batched_f32 / _c64 on A[:, jpvt] (Float32: where
+ *                            no pivot entry is exactly 0); dB after the solve has the bits of dhqr_solve_batched_nrhs_f32 /
+ *                            _c64 called with n = r, column by column, whatever nrhs, the column's place and the batch.
+ *   every other shape        (and every shape with the small route off) ComplexF64: ONE launch per call of the general
+ *                            kernels of csrc/dhqr_batched_complex_pivoted.h, a workgroup per matrix / per (matrix, column of
+ *                            B).  Float32: PROMOTED as everywhere -- float32(Float64 route(float64(.))): A (or the factor,
+ *                            alpha, B and X) widened, the Float64 pivoted route, the results rounded; jpvt is the Float64
+ *                            route's.
+ * The host forms stage through the buffers of dhqr_qr_batched_f32 / dhqr_qr_batched_c64 (dhqr_trim releases them). */
+int32_t dhqr_factor_batched_pivoted_f32(dhqr_ctx *ctx, float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                        float *dalpha, int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_rank_batched_f32(dhqr_ctx *ctx, const float *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond,
+                              int32_t *drank, int64_t batch);
+int32_t dhqr_solve_batched_pivoted_f32(dhqr_ctx *ctx, const float *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                       const float *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
+                                       const int32_t *drank, float *dB, int64_t nrhs, int64_t ldb, int64_t strideB, float *dX,
+                                       int64_t ldx, int64_t strideX, int64_t batch);
+int32_t dhqr_qr_batched_pivoted_f32(dhqr_ctx *ctx, float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, float *halpha,
+                                    int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_lstsq_batched_f32(dhqr_ctx *ctx, const float *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const float *hB,
+                               int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, float *hX, int64_t ldx, int64_t strideX,
+                               int32_t *hrank, int64_t batch);
+int32_t dhqr_factor_batched_pivoted_c64(dhqr_ctx *ctx, double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                        double *dalpha, int64_t stride_alpha, int32_t *djpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_rank_batched_c64(dhqr_ctx *ctx, const double *dalpha, int64_t m, int64_t n, int64_t stride_alpha, double rcond,
+                              int32_t *drank, int64_t batch);
+int32_t dhqr_solve_batched_pivoted_c64(dhqr_ctx *ctx, const double *dA, int64_t m, int64_t n, int64_t lda, int64_t strideA,
+                                       const double *dalpha, int64_t stride_alpha, const int32_t *djpvt, int64_t stride_jpvt,
+                                       const int32_t *drank, double *dB, int64_t nrhs, int64_t ldb, int64_t strideB, double *dX,
+                                       int64_t ldx, int64_t strideX, int64_t batch);
+int32_t dhqr_qr_batched_pivoted_c64(dhqr_ctx *ctx, double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, double *halpha,
+                                    int64_t stride_alpha, int32_t *hjpvt, int64_t stride_jpvt, int64_t batch);
+int32_t dhqr_lstsq_batched_c64(dhqr_ctx *ctx, const double *hA, int64_t m, int64_t n, int64_t lda, int64_t strideA, const double *hB,
                                int64_t nrhs, int64_t ldb, int64_t strideB, double rcond, double *hX, int64_t ldx, int64_t strideX,
                                int32_t *hrank, int64_t batch);
 

@@ -31,10 +31,11 @@ usage: python tools/batched_bench.py [--out FILE]          every point, each in 
                                                            caller had before: a loop of dhqr_apply_q_f64, one call per matrix
                                                            (on the first LOOP_BATCH matrices, scaled per matrix); ROUNDS
                                                            rounds of 10 repetitions each, every round's median listed
-       --pivot [--shapes ...] [--batches 16384]            what column pivoting costs: dhqr_factor_batched_pivoted_f64 +
-                                                           dhqr_rank_batched_f64 + dhqr_solve_batched_pivoted_f64 (one
-                                                           right-hand side) against dhqr_factor_batched_f64 +
-                                                           dhqr_solve_batched_f64 on the same resident data, at PIVOT_SHAPES
+       --pivot [--dtype f64|f32|c64] [--shapes ...] [--batches 16384]
+                                                           what column pivoting costs: dhqr_factor_batched_pivoted_* +
+                                                           dhqr_rank_batched_* + dhqr_solve_batched_pivoted_* (one
+                                                           right-hand side) against dhqr_factor_batched_* +
+                                                           dhqr_solve_batched_* on the same resident data, at PIVOT_SHAPES
                                                            with batch 16384 unless told otherwise; ROUNDS rounds of 10
                                                            repetitions, every round's median, and the factors alone
 
@@ -463,22 +464,28 @@ def main_applyq(a, shapes, batches):
 PIVOT_SHAPES = [(16, 8), (40, 17), (64, 32)]
 
 
-def point_pivot(m, n, batch):
-    """one point of --pivot: pivoted (factor + rank + truncated solve) and unpivoted (factor + solve) on the same inputs --
-    the project's generator with column c scaled by 1 + 0.25 c, full rank --, and each factor alone"""
+def point_pivot(m, n, batch, t="f64"):
+    """one point of --pivot: pivoted (factor + rank + truncated solve) and unpivoted (factor + solve) of the element type t on
+    the same inputs -- the project's generator with column c scaled by 1 + 0.25 c, full rank (f32: rounded) --, and each
+    factor alone"""
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as g
     pkg = g.import_package()
     os.environ["DHQR_SMALL"] = "1"
-    A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0")
-    A0 *= 1.0 + 0.25 * torch.arange(n, dtype=torch.float64, device="cuda:0")
-    b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    if t == "c64":
+        A0 = pkg.rand_colmajor_batched_c(batch, m, n, 1, "cuda:0")
+        b0 = pkg.rand_colmajor_batched_c(batch, m, 1, 7, "cuda:0").reshape(batch, m).contiguous()
+    else:
+        dt = torch.float32 if t == "f32" else torch.float64
+        A0 = pkg.rand_colmajor_batched(batch, m, n, 1, "cuda:0", dt)
+        b0 = pkg.rand_colmajor_batched(batch, m, 1, 7, "cuda:0", dt).reshape(batch, m).contiguous()
+    A0 *= (1.0 + 0.25 * torch.arange(n, dtype=torch.float64, device="cuda:0")).to(A0.dtype)
     A, b = A0.clone(), b0.clone()
-    al = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    al = torch.zeros((batch, n), dtype=A0.dtype, device="cuda:0")
     jp = torch.zeros((batch, n), dtype=torch.int32, device="cuda:0")
     rk = torch.zeros((batch,), dtype=torch.int32, device="cuda:0")
-    x = torch.zeros((batch, n), dtype=torch.float64, device="cuda:0")
+    x = torch.zeros((batch, n), dtype=A0.dtype, device="cuda:0")
     torch.cuda.synchronize()
     L, P, chk = pkg._lib.lib(), ctypes.c_void_p, pkg._lib.check
     pa, pal, pb, pjp, prk, px = (P(t.data_ptr()) for t in (A, al, b, jp, rk, x))
@@ -486,19 +493,19 @@ def point_pivot(m, n, batch):
     h = ctx.handle
 
     def f_piv():
-        chk(L.dhqr_factor_batched_pivoted_f64(h, pa, m, n, m, m * n, pal, n, pjp, n, batch))
+        chk(getattr(L, f"dhqr_factor_batched_pivoted_{t}")(h, pa, m, n, m, m * n, pal, n, pjp, n, batch))
 
     def f_plain():
-        chk(L.dhqr_factor_batched_f64(h, pa, m, n, m, m * n, pal, n, batch, 0))
+        chk(getattr(L, f"dhqr_factor_batched_{t}")(h, pa, m, n, m, m * n, pal, n, batch, 0))
 
     def pivoted():
         f_piv()
-        chk(L.dhqr_rank_batched_f64(h, pal, m, n, n, -1.0, prk, batch))
-        chk(L.dhqr_solve_batched_pivoted_f64(h, pa, m, n, m, m * n, pal, n, pjp, n, prk, pb, 1, m, m, px, n, n, batch))
+        chk(getattr(L, f"dhqr_rank_batched_{t}")(h, pal, m, n, n, -1.0, prk, batch))
+        chk(getattr(L, f"dhqr_solve_batched_pivoted_{t}")(h, pa, m, n, m, m * n, pal, n, pjp, n, prk, pb, 1, m, m, px, n, n, batch))
 
     def plain():
         f_plain()
-        chk(L.dhqr_solve_batched_f64(h, pa, m, n, m, m * n, pal, n, pb, m, batch))
+        chk(getattr(L, f"dhqr_solve_batched_{t}")(h, pa, m, n, m, m * n, pal, n, pb, m, batch))
 
     def measure(fn):
         rates = []
@@ -514,7 +521,7 @@ def point_pivot(m, n, batch):
                 rates.append(batch / dt)
         return {"median": statistics.median(rates), "min": min(rates), "max": max(rates)}
 
-    out = {"m": m, "n": n, "batch": batch, "pivoted": [], "plain": [], "factor_pivoted": [], "factor_plain": []}
+    out = {"m": m, "n": n, "batch": batch, "dtype": t, "pivoted": [], "plain": [], "factor_pivoted": [], "factor_plain": []}
     for _ in range(ROUNDS):
         out["pivoted"].append(measure(pivoted))
         xp = x.clone()
@@ -523,21 +530,23 @@ def point_pivot(m, n, batch):
         out["factor_pivoted"].append(measure(f_piv))
         out["factor_plain"].append(measure(f_plain))
     assert int(rk.min()) == n, "the inputs were meant to have full rank"
-    assert ((xp - xu).abs().amax(dim=1) <= 1e-9 * xp.abs().amax(dim=1)).all(), "pivoted and unpivoted solutions differ"
+    tol = 1e-3 if t == "f32" else 1e-9  # (two orders of the columns: the results differ by rounding times the condition number)
+    assert ((xp - xu).abs().amax(dim=1) <= tol * xp.abs().amax(dim=1)).all(), "pivoted and unpivoted solutions differ"
     ctx.close()
     print("POINT " + json.dumps(out), flush=True)
 
 
 def main_pivot(a, shapes, batches):
-    lines = [f"# tools/batched_bench.py --pivot: matrices per second, {ROUNDS} rounds of {REPS} repetitions in one process, every round's median, then min .. max over all repetitions",
-             "# pivoted = dhqr_factor_batched_pivoted_f64 + dhqr_rank_batched_f64 + dhqr_solve_batched_pivoted_f64 (one right-hand side, X written);",
-             "# unpivoted = dhqr_factor_batched_f64 + dhqr_solve_batched_f64; the same resident full-rank inputs; `factors` = the two factor calls alone"]
+    t = a.dtype
+    lines = [f"# tools/batched_bench.py --pivot --dtype {t}: matrices per second, {ROUNDS} rounds of {REPS} repetitions in one process, every round's median, then min .. max over all repetitions",
+             f"# pivoted = dhqr_factor_batched_pivoted_{t} + dhqr_rank_batched_{t} + dhqr_solve_batched_pivoted_{t} (one right-hand side, X written);",
+             f"# unpivoted = dhqr_factor_batched_{t} + dhqr_solve_batched_{t}; the same resident full-rank inputs; `factors` = the two factor calls alone"]
     print("\n".join(lines), flush=True)
     rc = 0
     for (m, n) in shapes:
         for batch in batches:
             p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--point",
-                                str(m), str(n), str(batch), "--pivot"], capture_output=True, text=True)
+                                str(m), str(n), str(batch), "--pivot", "--dtype", t], capture_output=True, text=True)
             row = [ln for ln in p.stdout.splitlines() if ln.startswith("POINT ")]
             if p.returncode != 0 or not row:
                 lines.append(f"{m}x{n} batch {batch}: FAILED (exit {p.returncode}); stopping\n{p.stderr[-2000:]}")
@@ -548,7 +557,7 @@ def main_pivot(a, shapes, batches):
             med = lambda rs: statistics.median(v["median"] for v in rs)
             rounds = lambda rs: " ".join(f"{v['median']:.0f}" for v in rs) + f" ({min(v['min'] for v in rs):.0f} .. {max(v['max'] for v in rs):.0f})"
             ratios = " ".join("%.3f" % (x["median"] / y["median"]) for x, y in zip(r["pivoted"], r["plain"]))
-            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} | pivoted {rounds(r['pivoted'])} | unpivoted {rounds(r['plain'])} | "
+            txt = (f"{m:4d} x {n:<4d} batch {r['batch']:6d} {t} | pivoted {rounds(r['pivoted'])} | unpivoted {rounds(r['plain'])} | "
                    f"pivoted/unpivoted per round {ratios} | "
                    f"median {med(r['pivoted']) / med(r['plain']):5.2f}x | factors: pivoted {med(r['factor_pivoted']):.0f} unpivoted "
                    f"{med(r['factor_plain']):.0f} ratio {med(r['factor_pivoted']) / med(r['factor_plain']):5.2f}x")
@@ -625,7 +634,7 @@ def main():
     a = ap.parse_args()
     if a.point:
         if a.pivot:
-            point_pivot(*a.point)
+            point_pivot(*a.point, a.dtype)
         elif a.arm is not None:
             point_arm(*a.point, a.nrhs or 16, a.arm)
         elif a.applyq is not None:
